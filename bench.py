@@ -11,21 +11,36 @@ the 512^3 headline and per-GPU work is fixed as N grows.
 A "step" is one fields::step() (src/step.cpp:35-140) over the whole grid.
 value = (all cells * K) / max-over-ranks wall time, in Mcells*steps/s.
 
-At N=1 the same JSON line also carries the other single-GPU BASELINE configs,
-measured in the same run ("configs"): C2 256^3 vacuum + PML, C4 256^3 Kerr +
-Lorentzian slab, and C4's chi(2) Newton-Raphson sub-variant (NR solves/s).
+A plain run does what the headline figure needs and nothing else: set-up, tuning,
+warm-up, the K timed steps, the result line.  --full adds everything else the line can
+carry.  At N=1 those are the other single-GPU BASELINE configs ("configs": C2 256^3
+vacuum + PML, C4 256^3 Kerr + Lorentzian slab, C4's chi(2) Newton-Raphson sub-variant
+(NR solves/s), the headline grid with 4 DFT flux planes), the CPU baseline
+("cpu_baseline") and the GPU's clocks and power ("gpu_state").  At N>1 they are C5 on
+the ranks of the run ("configs") and the C5 self-check against the one-rank fixture
+("c5_parity").  The --no-* switches below take single legs out of a --full run.
+
+--dump-outputs DIR writes what the timed steps left in the fields, as a caller of
+Fields.get_array receives it after the last timed step: per component a dense block
+around the grid centre (where the source is) and a seeded sample of the whole array,
+DIR/<component>_center.npy and DIR/<component>_sample.npy (float64, 48 MB in all).
+The inputs are fixed, so two builds run with the same arguments compare file by file.
+(Tuning steps the fields for real.  It takes the same number of steps in every run of
+the headline; with polarization chunks -- kerr, kerr_nr -- the candidates of the CU split
+follow from measured times, so compare those workloads with --no-tune.)
 
 BASELINE configs[4] (C5: 1024x512x512 cells z-slab-decomposed over 8 GPUs) is
 --workload c5: vacuum + PML(1.0), 512 x 512 x 128 cells per GPU, global
 512 x 512 x (128*N) (the long axis is the slab axis z).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--vacuum]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--vacuum] [--full]
+                   [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 --gpus N without a launcher starts N ranks under torch.distributed.run (child
 processes).  Ranks sharing a GPU (MNL_BENCH_DEVICE, or fewer GPUs than ranks)
 exchange ghost planes over the IPC transport, otherwise over RCCL.
-Prints ONE JSON line on rank 0 (with "roofline" and "cpu_baseline").
+Prints ONE JSON line on rank 0 (with "roofline"; --full: "cpu_baseline", "configs", ...).
 """
 import argparse
 import gc
@@ -56,14 +71,20 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the other "
+                         "configs, the CPU baseline, the multi-GPU self-check, GPU clocks / power")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields of the last timed step (a centre block and a seeded "
+                         "sample of every component) as DIR/<name>.npy")
     ap.add_argument("--no-tune", action="store_true",
                     help="keep the default knobs (skip Fields.tune before the warm-up)")
     ap.add_argument("--size", type=int, default=512, help="cells per side of each GPU's slab")
     ap.add_argument("--vacuum", action="store_true", help="north-star vacuum variant (no core)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the C2 / C4 / C4-NR measurements (N=1)")
+                    help="--full: skip the C2 / C4 / C4-NR / flux measurements (N=1), C5 (N>1)")
     ap.add_argument("--extra-size", type=int, default=256)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--flux", type=int, default=0,
@@ -72,9 +93,9 @@ def parse():
     ap.add_argument("--no-events", action="store_true",
                     help="diagnostics: no per-kernel HIP events in the timed region")
     ap.add_argument("--no-parity", action="store_true",
-                    help="N > 1: skip the C5 self-check against the one-rank fixture")
+                    help="--full, N > 1: skip the C5 self-check against the one-rank fixture")
     ap.add_argument("--no-smi", action="store_true",
-                    help="do not query rocm-smi for clocks / power (gpu_state)")
+                    help="--full: do not query rocm-smi for clocks / power (gpu_state)")
     return ap.parse_args()
 
 
@@ -504,6 +525,40 @@ def measure_c5(args, rank, world, device, dist):
     return out
 
 
+DUMP_BLOCK = 64        # --dump-outputs: cells per side of the dense block at the grid centre
+DUMP_SAMPLE = 1 << 18  # and entries of the seeded sample of the whole array, per component
+DUMP_SEED = 20240519
+
+
+def dump_outputs(f, gv, path, rank=0, world=1, dist=None):
+    """--dump-outputs: every component as Fields.get_array returns it after the last timed
+    step, cut down to a dense DUMP_BLOCK^3 block around the grid centre (the source sits
+    there, so after a few dozen steps that is where the field is) and DUMP_SAMPLE entries of
+    the whole array at seeded positions: path/<component>_center.npy and _sample.npy, float64,
+    12 x 2 x 2 MiB.  On several ranks every entry has one owner and is 0 elsewhere, so the
+    ranks' cuts add up exactly to the global array's; rank 0 writes them."""
+    import numpy as np
+    from meep_nl_amd import core
+    shape = tuple(int(v) for v in gv.shape())
+    ntot = int(np.prod(shape))
+    block = tuple(slice(max(0, n // 2 - DUMP_BLOCK // 2), min(n, n // 2 + DUMP_BLOCK // 2))
+                  for n in shape)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, ntot, size=min(DUMP_SAMPLE, ntot)))
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+    for c, name in enumerate(core.COMPONENT_NAMES):
+        a = f.get_array(c)
+        cuts = {"center": np.ascontiguousarray(a[block]), "sample": a.reshape(-1)[idx]}
+        del a
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, cuts)
+            cuts = {k: np.sum([p[k] for p in parts], axis=0) for k in cuts}
+        if rank == 0:
+            for k, v in cuts.items():
+                np.save(os.path.join(path, f"{name}_{k}.npy"), v.astype(np.float64, copy=False))
+
+
 def cpu_baseline(args):
     """Time the oracle (CPU restatement, oracle/) on the headline config itself: the
     512^3 waveguide (eps = 12 core) + PML(1.0) with the same Gaussian source, OpenMP on this
@@ -616,19 +671,6 @@ def main():
     # untimed set-up: the fused step's knobs timed over real steps (identical results)
     zc = None if args.no_tune else f.tune()
     f.step(args.warmup)
-    # GPU clocks / power sampled while this rank keeps stepping (untimed, <= 10 s), and
-    # again right after the timed region
-    state_busy = None
-    if not args.no_smi:
-        proc = gpu_state_start() if rank == 0 else None
-        if world == 1:
-            t_s = time.perf_counter()
-            while proc is not None and proc.poll() is None and time.perf_counter() - t_s < 10:
-                f.step(10)
-        else:  # every rank steps the same count (the steps are collective)
-            f.step(100)
-        if proc is not None:
-            state_busy = gpu_state_finish(proc)
     if args.flux:  # no DFT update of the warm-up left buffered for the timed region
         f.dft_flush()
     barrier()
@@ -640,7 +682,6 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     el_own = el
-    state_after = gpu_state_finish(gpu_state_start()) if rank == 0 and not args.no_smi else None
     if dist is not None:
         import torch
         t = torch.tensor([el], dtype=torch.float64)
@@ -668,10 +709,28 @@ def main():
     if dist is not None:  # per-rank pair / rim / slab-face chain / exchange-wait breakdown
         per_rank = [None] * world
         dist.all_gather_object(per_rank, rank_breakdown(f, rank, el_own / args.steps * 1e3))
+    if args.dump_outputs:
+        dump_outputs(f, gv, args.dump_outputs, rank, world, dist)
+    # --full: GPU clocks / power sampled while this rank keeps stepping (<= 10 s), and again
+    # idle.  After the timed steps and the dump, so that neither depends on how long the
+    # query took
+    state_busy = state_after = None
+    if args.full and not args.no_smi:
+        f.set_profiling(False)
+        proc = gpu_state_start() if rank == 0 else None
+        if world == 1:
+            t_s = time.perf_counter()
+            while proc is not None and proc.poll() is None and time.perf_counter() - t_s < 10:
+                f.step(10)
+        else:  # every rank steps the same count (the steps are collective)
+            f.step(100)
+        if proc is not None:
+            state_busy = gpu_state_finish(proc)
+        state_after = gpu_state_finish(gpu_state_start()) if rank == 0 else None
     del f, s
     gc.collect()
     extra = None
-    if world > 1 and not args.no_extra and args.workload != "c5":
+    if args.full and world > 1 and not args.no_extra and args.workload != "c5":
         # BASELINE configs[4] (C5) in the same multi-GPU run: 512 x 512 x 128 vacuum + PML
         # per GPU, its own communicator, timed the same way (max over ranks)
         try:
@@ -679,7 +738,7 @@ def main():
         except Exception as e:  # never hides the headline number
             extra = {"c5": {"error": str(e)}}
     parity = None
-    if world > 1 and not args.no_parity:
+    if args.full and world > 1 and not args.no_parity:
         try:
             parity = c5_parity(args, rank, world, device, dist)
         except Exception as e:  # never hides the headline number
@@ -688,7 +747,7 @@ def main():
         if dist is not None:
             dist.barrier()
         return
-    if world == 1 and not args.no_extra and not args.flux:
+    if args.full and world == 1 and not args.no_extra and not args.flux:
         extra = {}
         for wl in ("c2", "kerr", "kerr_nr"):
             try:
@@ -705,7 +764,8 @@ def main():
         except Exception as e:
             extra["flux4"] = {"error": str(e)}
     cpu = None
-    if world == 1 and not args.no_cpu and args.workload in ("waveguide", "vacuum") and not args.flux:
+    if (args.full and world == 1 and not args.no_cpu and args.workload in ("waveguide", "vacuum")
+            and not args.flux):
         try:
             cpu = cpu_baseline(args)
         except Exception as e:  # the baseline must never hide the GPU number
@@ -718,6 +778,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(el / args.steps * 1e3, 4),
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,

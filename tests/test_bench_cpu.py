@@ -15,10 +15,65 @@ def test_defaults_and_driver_flags(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup, a.size) == (1, 60, 10, 512)
     assert not a.no_tune and a.workload is None
+    assert not a.full and a.dump_outputs is None  # a plain run: the headline figure alone
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "7", "--warmup", "3",
                                       "--no-tune", "--workload", "c5"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup, a.no_tune, a.workload) == (8, 7, 3, True, "c5")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2",
+                                      "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+class _FakeFields:
+    """get_array of a seeded random state (dump_outputs needs nothing else of the fields)."""
+
+    def __init__(self, shape, seed):
+        self.shape, self.seed = shape, seed
+
+    def get_array(self, comp):
+        import numpy as np
+        return np.random.default_rng(self.seed + comp).standard_normal(self.shape)
+
+
+class _FakeGrid:
+    def __init__(self, shape):
+        self._shape = shape
+
+    def shape(self):
+        return self._shape
+
+
+def test_dump_outputs_cuts(tmp_path):
+    """--dump-outputs: per component the dense block around the grid centre and the seeded
+    sample are entries of get_array's array itself, float64, at the same positions from run
+    to run, for a grid smaller and one larger than the block; the 512^3 headline's files stay
+    under 64 MB in all."""
+    import numpy as np
+    import bench
+    from meep_nl_amd import core
+    assert 12 * 8 * (bench.DUMP_BLOCK ** 3 + bench.DUMP_SAMPLE) <= 64e6
+    for shape in ((9, 7, 11), (bench.DUMP_BLOCK + 9, bench.DUMP_BLOCK + 2, bench.DUMP_BLOCK + 5)):
+        f, gv = _FakeFields(shape, 3), _FakeGrid(shape)
+        d1, d2 = str(tmp_path / f"a{shape[0]}"), str(tmp_path / f"b{shape[0]}")
+        bench.dump_outputs(f, gv, d1)
+        bench.dump_outputs(f, gv, d2)
+        assert sorted(os.listdir(d1)) == sorted(f"{n}_{k}.npy" for n in core.COMPONENT_NAMES
+                                                for k in ("center", "sample"))
+        want = tuple(min(n, bench.DUMP_BLOCK) for n in shape)
+        for c, name in enumerate(core.COMPONENT_NAMES):
+            a = f.get_array(c)
+            cen = np.load(os.path.join(d1, f"{name}_center.npy"))
+            sam = np.load(os.path.join(d1, f"{name}_sample.npy"))
+            assert cen.dtype == sam.dtype == np.float64 and cen.shape == want
+            lo = [n // 2 - w // 2 for n, w in zip(shape, want)]
+            assert np.array_equal(cen, a[lo[0]:lo[0] + want[0], lo[1]:lo[1] + want[1],
+                                         lo[2]:lo[2] + want[2]])
+            assert sam.shape == (min(bench.DUMP_SAMPLE, a.size),) and np.isin(sam, a).all()
+            for k in ("center", "sample"):
+                assert np.array_equal(np.load(os.path.join(d2, f"{name}_{k}.npy")),
+                                      cen if k == "center" else sam)
 
 
 def test_workloads_cover_the_baseline_configs():
