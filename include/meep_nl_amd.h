@@ -236,15 +236,18 @@ int mnl_fields_require_component(mnl_fields *f, int comp);
  * centre (src/step.cpp:138-139) every `every` steps, counted across calls (default
  * 100): fails with "meep: simulation fields are NaN or Inf". */
 int mnl_fields_step(mnl_fields *f, int nsteps);
-/* No reference counterpart (tuning knobs of this implementation).  Times, over real steps
- * (one warm-up and `reps` timed steps per candidate): (1) the tile kernel's z-chunk length
- * (automatic, 16, 20, 24, 32, 48; skipped with MNL_FUSED_ZCHUNK set), (2) on one rank with
- * polarization chunks, the CUs of their general kernel running beside the tile kernel
- * (0 and five splits around the balanced one; skipped with MNL_TILE_GEN_CUS set), and keeps
- * the fastest; with temporal blocking also the planes of the two-step
- * items (automatic, 32, 48, 64, 96, 128) and pairs vs one-step stepping.  Each candidate: two warm-up steps, reps (rounded up to even) timed.  Advances the
- * fields by at most 2 + 19 * (2 + reps) steps, with results
- * identical to plain stepping.  *zchunk = the length kept (0 = automatic), *gen_cus = the
+/* No reference counterpart (tuning knobs of this implementation).  Times, over real steps:
+ * (1) the tile kernel's z-chunk length (automatic, 16, 20, 24, 32, 48: 6 runs; skipped with
+ * MNL_FUSED_ZCHUNK set), (2) on one rank, the CUs of the polarization chunks' general kernel
+ * running beside the tile kernel (0, and with such chunks up to five splits around the balanced
+ * one: up to 6 runs; skipped with MNL_TILE_GEN_CUS set), and keeps the fastest; with temporal
+ * blocking also (3) the two-step items' planes and width: 124 columns
+ * with automatic, 12, 16, 20, 24, 32, 40, 48, 64, 96, 128 planes and 60 columns with automatic,
+ * 12, 16, 20, 24, 32, 40, 48 planes (19 candidates, swept forward and backward: 38 runs; the
+ * three best again with 2 * reps timed steps), and (4) pairs vs one-step stepping (one run,
+ * and one with 2 * reps timed steps).  A run is two warm-up steps and r timed ones, r = reps
+ * rounded up to even.  Advances the fields by at most 2 + 51 * (2 + r) + 4 * (2 + 2 * reps)
+ * steps (112 + 59 * reps for even reps), with results identical to plain stepping.  *zchunk = the length kept (0 = automatic), *gen_cus = the
  * CUs kept (0 = one launch after the other); -1 = not tuned (not in the fused tile mode:
  * at most 2 steps taken). */
 int mnl_fields_tune(mnl_fields *f, int reps, int *zchunk, int *gen_cus);
@@ -369,9 +372,7 @@ int mnl_fields_kernel_stats(mnl_fields *f, int which, long long *launches, doubl
  * first two-step item (the longest), narrow x-face strip items among the rim items,
  * enabled (pairs allowed: set_temporal_blocking / MNL_TB / the tuner), the two-step chunk
  * setting (0: automatic), the most own columns of a two-step item (124 unless set or tuned),
- * polarization chunks stepped inside the pairs (1), interior two-step items (their two-step
- * footprint meets no rim box; one rank runs them beside the previous pair's second rim
- * launch). */
+ * polarization chunks stepped inside the pairs (1). */
 int mnl_fields_tb_info(mnl_fields *f, double *out, int n);
 /* Allow (1, the default; MNL_TB=0 at creation turns it off) or forbid (0) stepping
  * pairs of steps with the two-step kernel.  Results are identical either way. */
@@ -386,18 +387,13 @@ int mnl_fields_set_temporal_blocking(mnl_fields *f, int on);
  * 6 planes per rim item of a pair (value; 0 = the one-step chunk length), 7 the chi(2) NR box's
  * E phase beside the tile kernel (MNL_NR_EARLY), 8 planes per two-step item (value; 0 =
  * automatic; MNL_TB_ZCHUNK), 9 the most own columns of a two-step item (value 4..124; 0 = 124,
- * the widest the kernel's 128 columns of lanes hold), 10 columns per lane of the two-step kernel
- * (2; 1 = the round-5 kernel; MNL_TB_PX), 11 pairs of steps with polarization chunks (1, the
- * default; MNL_TB_POL), 12 the first rim launch's items other than the narrow x-face strips on a
- * side stream beside the two-step kernel (1, the default; one rank; MNL_TB_R1A), 13 the
- * interior two-step items on a third stream beside the previous pair's second rim launch (1;
- * 0, the default: measured slower at 512^3; one rank, no DFT monitors;
- * MNL_TB_LINT), 14 the second rim launch's item order (1 longest first, 2 narrow strips
- * first; 0, the default: the first launch's order, narrow strips last, measured faster; one
- * rank; MNL_TB_R2LPT), 15 planes per narrow x-face strip item of the rim (value; 0 = the rim's
- * chunk length; MNL_TB_STRIP_ZCHUNK), 16 a pair's step sources and NaN guard in one launch (1,
- * the default; one rank; MNL_TB_SRCGUARD).  For in-process A/B measurements
- * (tools/ab_inproc.py). */
+ * the widest the kernel's 128 columns of lanes hold), 11 pairs of steps with polarization chunks
+ * (1, the default; MNL_TB_POL), 12 the first rim launch's items other than the narrow x-face
+ * strips on a side stream beside the two-step kernel (1, the default; one rank; MNL_TB_R1A),
+ * 16 a pair's step sources and NaN guard in one launch (1, the default; one rank;
+ * MNL_TB_SRCGUARD).  For in-process A/B measurements (tools/ab_inproc.py).  10, 13, 14 and 15
+ * are retired (variants measured slower or no better and since removed):
+ * they fail like any unknown number. */
 int mnl_fields_set_schedule(mnl_fields *f, int which, int value);
 
 /* ---- checkpoint (src/fields_dump.cpp, src/structure_dump.cpp) -----------

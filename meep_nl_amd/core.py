@@ -399,9 +399,14 @@ class Fields:
         """Time the fused step's knobs over real steps and keep the fastest (mnl_fields_tune:
         the tile kernel's z-chunk length, then on one rank with polarization chunks the CUs
         of their general kernel beside the tile kernel; with temporal blocking the planes and
-        widths of its two-step items).  Every candidate runs two warm-up steps and reps
-        (rounded up to even) timed ones: at most 2 + 32 * (2 + reps) steps, results identical
-        to plain stepping (round 6: 8 timed steps by default, 4 gave choices off by up to 10 %
+        widths of its two-step items and pairs against one-step stepping).  A run is two
+        warm-up steps and r timed ones, r = reps rounded up to even: 6 runs for the z-chunk
+        (automatic, 16, 20, 24, 32, 48), up to 6 for the CUs (0 and five splits), 38 for the
+        two-step items (124 columns x automatic, 12, 16, 20, 24, 32, 40, 48, 64, 96, 128
+        planes and 60 columns x automatic, 12 .. 48 planes: 19 candidates, forward and
+        backward) and the three best again with 2 * reps timed steps, one for one-step
+        stepping and one more with 2 * reps.  At most 2 + 51 * (2 + r) + 4 * (2 + 2 * reps)
+        steps (112 + 59 * reps for even reps), results identical to plain stepping (round 6: 8 timed steps by default, 4 gave choices off by up to 10 %
         at 256^3).  Returns (zchunk, gen_cus); -1 = not tuned (not in the fused tile mode)."""
         z, g = ctypes.c_int(0), ctypes.c_int(0)
         check(lib().mnl_fields_tune(self.h, int(reps), ctypes.byref(z), ctypes.byref(g)))
@@ -588,20 +593,15 @@ class Fields:
         boxes, 'rim_zchunk' = planes per rim item of a pair (an integer; 0 the one-step chunk),
         'nr_early' = the chi(2) NR box's E phase beside the tile kernel, 'tb_zchunk' = planes per
         two-step item (an integer; 0 automatic), 'tb_ox' = the most own columns of a two-step
-        item (4..124; 0 = 124), 'tb_px' = columns per lane of the two-step kernel (2; 1 = the
-        round-5 kernel, kept for A/B), 'tb_pol' = pairs of steps with polarization chunks
-        (their general kernel one step at a time beside the rim launches), 'r1_beside' = the
-        first rim launch's items other than the narrow strips on a side stream beside the
-        two-step kernel, 'tb_lint' = the interior two-step items on a third stream beside the
-        previous pair's second rim launch, 'r2_lpt' = the second rim launch in longest-first
-        order (the first keeps the narrow strips last), 'strip_zchunk' = planes per narrow
-        x-face strip item of the rim (0: the rim's), 'src_guard' = a pair's step sources and
-        NaN guard in one launch (mnl_fields_set_schedule)."""
+        item (4..124; 0 = 124), 'tb_pol' = pairs of steps with polarization chunks (their
+        general kernel one step at a time beside the rim launches), 'r1_beside' = the first rim
+        launch's items other than the narrow strips on a side stream beside the two-step
+        kernel, 'src_guard' = a pair's step sources and NaN guard in one launch
+        (mnl_fields_set_schedule; its numbers 10, 13, 14 and 15 are retired)."""
         idx = {"narrow": 0, "dft_pal": 1, "res": 2, "res_tb2": 3, "res_rim": 4, "dft_cmp": 5,
-               "rim_zchunk": 6, "nr_early": 7, "tb_zchunk": 8, "tb_ox": 9, "tb_px": 10,
-               "tb_pol": 11, "r1_beside": 12, "tb_lint": 13, "r2_lpt": 14,
-               "strip_zchunk": 15, "src_guard": 16}[which]
-        if idx in (2, 3, 4, 6, 8, 9, 10, 13, 14, 15):  # integers: CUs left free (-1: the default), planes
+               "rim_zchunk": 6, "nr_early": 7, "tb_zchunk": 8, "tb_ox": 9, "tb_pol": 11,
+               "r1_beside": 12, "src_guard": 16}[which]
+        if idx in (2, 3, 4, 6, 8, 9):  # integers: CUs left free (-1: the default), planes, columns
             check(lib().mnl_fields_set_schedule(self.h, idx, int(value)))
         else:
             check(lib().mnl_fields_set_schedule(self.h, idx, 1 if value else 0))
@@ -611,15 +611,13 @@ class Fields:
         active (the last call of >= 2 steps stepped in pairs), two-step own cells / border
         points / mixed-palette cells, rim cells / mixed-palette rim cells, item counts, the
         first item's planes, the narrow x-face strip items among the rim items, the
-        two-step chunk setting (0: automatic), the most own columns of a two-step item,
-        whether polarization chunks step inside the pairs and the interior two-step items (their
-        footprint meets no rim box: one rank runs them beside the previous pair's second rim
-        launch)."""
-        v = (ctypes.c_double * 15)()
-        check(lib().mnl_fields_tb_info(self.h, v, 15))
+        two-step chunk setting (0: automatic), the most own columns of a two-step item and
+        whether polarization chunks step inside the pairs."""
+        v = (ctypes.c_double * 14)()
+        check(lib().mnl_fields_tb_info(self.h, v, 14))
         keys = ("active", "tb_cells", "tb_border", "tb_cells_mixed", "rim_cells",
                 "rim_cells_mixed", "tb_items", "rim_items", "tb_planes", "narrow_items", "enabled",
-                "tb_zchunk", "tb_width", "tb_pol", "tb_interior_items")
+                "tb_zchunk", "tb_width", "tb_pol")
         flags = ("active", "enabled", "tb_pol")
         return {k: (bool(x) if k in flags else int(x)) for k, x in zip(keys, v)}
 

@@ -2651,11 +2651,10 @@ int dev_upload(mnl_fields *F, T **d, size_t &cap, const std::vector<T> &h) {
 // Build (or keep) the plan of the current fused geometry and source points.  No plan (tb_have
 // false) when L2 is empty or an item would not fit the kernels' shapes.
 int tb_plan(mnl_fields *F) {
-  F->tb_r1done_ok = false;
   unsigned long long sig = 1469598103934665603ULL;
   auto mix = [&](long long v) { sig = (sig ^ (unsigned long long)v) * 1099511628211ULL; };
   mix(F->fused_epoch), mix(F->tb_zchunk), mix(F->fused_zchunk), mix((long long)F->nlocal);
-  mix(F->rim_zchunk), mix(F->tb_ox), mix(F->tb_px), mix(F->tb_pol_on), mix(F->tb_lint != 0), mix(F->tb_r2lpt), mix(F->tb_szc);
+  mix(F->rim_zchunk), mix(F->tb_ox), mix(F->tb_pol_on);
   mix((long long)F->srcD_idx.size());
   for (long long v : F->srcD_idx) mix(v);
   // DFT monitors (one rank): the Yee points their samples average, +1 along every axis --
@@ -2854,11 +2853,8 @@ int tb_plan(mnl_fields *F) {
     std::sort(zcut.begin(), zcut.end());
     zcut.erase(std::unique(zcut.begin(), zcut.end()), zcut.end());
     std::sort(zcut.begin(), zcut.end());
-    // narrow strips: their own planes per item (tb_szc; one strip pair per workgroup, so the
-    // strips of a 512^3 rim make only ~200 workgroups at the rim's chunk length)
-    const int zcb = narrow && F->tb_szc > 0 ? std::min(F->tb_szc, FUSED_MAXCH) : zc;
     for (size_t s = 0; s + 1 < zcut.size(); s++) {
-      const int n = zcut[s + 1] - zcut[s], nt = (n + zcb - 1) / zcb;
+      const int n = zcut[s + 1] - zcut[s], nt = (n + zc - 1) / zc;
       for (int t = 0; t < nt; t++) zs.push_back(zcut[s] + (int)((long long)n * t / nt));
     }
     zs.push_back(b.hi[2] + 1);
@@ -2962,12 +2958,8 @@ int tb_plan(mnl_fields *F) {
         if (it.dep == (dep == 1)) order.push_back(it);
   // one rank: the narrow strips (they read the two-step kernel's output) last, so that R1's
   // other items can run beside the two-step kernel (tb_pair, tb_r1a).  The second rim launch
-  // reads a second copy of the list after the first: the same order by default (measured
-  // faster than longest first, tb_r2lpt: 512^3 -0.8 %, C2 256^3 -3.6 %)
-  std::vector<RI> order2 = order;
-  if (F->tb_r2lpt == 2)  // the narrow strips first
-    std::stable_partition(order2.begin(), order2.end(),
-                          [](const RI &r) { return ((r.code >> 30) & 1) != 0; });
+  // takes the same list in the same order (its own longest-first order measured slower:
+  // 512^3 +0.8 %, C2 256^3 +3.6 %)
   F->tb_rs0 = (int)order.size();
   if (F->nranks == 1) {
     auto strip = [](const RI &r) { return ((r.code >> 30) & 1) != 0; };
@@ -2977,25 +2969,21 @@ int tb_plan(mnl_fields *F) {
   }
   F->tb_rfree = 0;
   for (const RI &it : order) F->tb_rfree += it.dep ? 0 : 1;
-  const std::vector<RI> *lists[2] = {&order, (F->nranks == 1 && F->tb_r2lpt) ? &order2 : &order};
-  for (const std::vector<RI> *v : lists)
-    for (const RI &it : *v) {
-      F->tb_ritems.push_back(it.code);
-      F->tb_rgeo.push_back(it.g0), F->tb_rgeo.push_back(it.g1), F->tb_rgeo.push_back(it.g2);
-      F->tb_rgeo.push_back(it.g3);
-    }
+  for (const RI &it : order) {
+    F->tb_ritems.push_back(it.code);
+    F->tb_rgeo.push_back(it.g0), F->tb_rgeo.push_back(it.g1), F->tb_rgeo.push_back(it.g2);
+    F->tb_rgeo.push_back(it.g3);
+  }
   // ---- two-step items: up to 124 x 12 own points (128 x 16 columns of lanes, two per lane),
   // z chunks of tz planes (automatic: the length whose item count fills whole rounds of one
   // workgroup per CU best, with the three halo planes of a chunk as overhead)
   // own columns of the two-step items: x0 .. x1 with lane 0's first column lx = x0 - 2 (x0 - 3
   // when x0 is odd: lane loads are 16-byte aligned), x1 <= lx + 125 and at most tb_ox columns
   // (0: TB_OXW = 124); widths of a box are whole pieces of that width plus the remainder
-  // (tb_px = 1, the round-5 kernel for A/B: 60 own columns, lane 0 at x0 - 2, 64 lanes)
-  const int px = F->tb_px;
-  const int oxw = F->tb_ox ? F->tb_ox : (px == 1 ? 60 : TB_OXW);
-  auto lane0 = [px](int x0) { return px == 1 ? x0 - 2 : (x0 & 1) ? x0 - 3 : x0 - 2; };
+  const int oxw = F->tb_ox ? F->tb_ox : TB_OXW;
+  auto lane0 = [](int x0) { return (x0 & 1) ? x0 - 3 : x0 - 2; };
   auto next_x1 = [&](int x0, int hi) {
-    return std::min(std::min(lane0(x0) + TB_LX * px - 3, x0 + oxw - 1), hi);
+    return std::min(std::min(lane0(x0) + TB_LX * TB_PX - 3, x0 + oxw - 1), hi);
   };
   auto box_items_x = [&](const Box &b) {
     int n = 0;
@@ -3127,44 +3115,27 @@ int tb_plan(mnl_fields *F) {
           F->tb_border += nb;  // an upper bound (edges counted twice)
         }
   }
-  // the work queue takes the items in list order: longest first.  One rank: the items whose
-  // two-step footprint (own box + 2) meets no rim box first -- they read only what the previous
-  // pair's two-step kernel wrote, so they can run beside that pair's second rim launch
-  // (tb_pair, tb_lint) -- then the others
-  auto interior = [&](const TB2Item &it) {
-    Box o;
-    o.lo[0] = (it.x & 0xFFFF) - 2, o.hi[0] = (it.x >> 16) + 2;
-    o.lo[1] = (it.y & 0xFFFF) - 2, o.hi[1] = (it.y >> 16) + 2;
-    o.lo[2] = (it.z & 0xFFFF) - 2, o.hi[2] = (it.z >> 16) + 1;
-    for (const Box &r : rim)
-      if (box_meets(o, r)) return false;
-    return (it.faces & 63) == 0;
-  };
+  // the work queue takes the items in list order: longest first
   std::stable_sort(items.begin(), items.end(), [](const TB2Item &p, const TB2Item &q) {
     return (p.z >> 16) - (p.z & 0xFFFF) > (q.z >> 16) - (q.z & 0xFFFF);
   });
-  F->tb_nint = 0;
-  if (F->nranks == 1) {
-    for (const TB2Item &it : items) F->tb_nint += interior(it) ? 1 : 0;
-    if (F->tb_lint) std::stable_partition(items.begin(), items.end(), interior);
-  }
   F->tb_items = items;
   // ---- upload, palette-uniform flags, mixed-palette cell counts (traffic model)
   if (dev_upload(F, &F->d_tb_ritems, F->tb_rcap, F->tb_ritems) ||
       dev_upload(F, &F->d_tb_rgeo, F->tb_gcap, F->tb_rgeo) ||
       dev_upload(F, &F->d_tb_items, F->tb_icap, F->tb_items))
     return -1;
-  const int nr = (int)F->tb_ritems.size() / 2, ni = (int)F->tb_items.size();  // two copies
+  const int nr = (int)F->tb_ritems.size(), ni = (int)F->tb_items.size();
   if (F->d_tb_rflag) (void)hipFree(F->d_tb_rflag);
   if (F->d_tb_uflag) (void)hipFree(F->d_tb_uflag);
   F->d_tb_rflag = F->d_tb_uflag = nullptr;
   F->rim_cells_nu = F->rim_cells;
   F->tb_cells_nu = F->tb_cells;
   if (F->d_uidx) {
-    HIPCHK(hipMalloc(&F->d_tb_rflag, std::max(2 * nr, 1) * sizeof(unsigned)));
+    HIPCHK(hipMalloc(&F->d_tb_rflag, std::max(nr, 1) * sizeof(unsigned)));
     HIPCHK(hipMalloc(&F->d_tb_uflag, std::max(ni, 1) * sizeof(unsigned)));
     FusedArgs fa = fused_args(F);  // strides / palette of the current arrays
-    if (k_tile_items_uniform(fa, F->d_tb_ritems, F->d_tb_rgeo, 2 * nr, F->d_tb_rflag, F->stream))
+    if (k_tile_items_uniform(fa, F->d_tb_ritems, F->d_tb_rgeo, nr, F->d_tb_rflag, F->stream))
       return fail("rim palette flags failed");
     TB2Args t{};
     t.n = ni, t.items = F->d_tb_items, t.uidx = F->d_uidx;
@@ -3310,7 +3281,7 @@ FusedArgs rim_args(mnl_fields *F, const FusedArgs &fa, const Set5 &o, const Set5
   r.titems = F->d_tb_ritems;
   r.tgeo = F->d_tb_rgeo;
   r.tflag = F->d_uidx ? F->d_tb_rflag : nullptr;
-  r.gbeg = 0, r.gend = (int)F->tb_ritems.size() / 2;
+  r.gbeg = 0, r.gend = (int)F->tb_ritems.size();
   r.clk.kind = 1;
   return r;
 }
@@ -3352,7 +3323,6 @@ TB2Args tb_args(mnl_fields *F, const Set5 &o, const Set5 &m, const Set5 &n) {
   t.clk = ItemClock{F->d_clk, F->d_clk_n, F->d_clk ? CLK_CAP : 0u, 2};
   t.ncmp = (int)F->tb_cmp.size();
   for (int i = 0; i < t.ncmp; i++) t.cmp[i] = F->tb_cmp[i];
-  t.px = F->tb_px;
   return t;
 }
 
@@ -3431,7 +3401,7 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
   const FusedArgs &fa = fused_args(F);
   const Set5 cur = set_cur(F), mid = set_mid(F), nxt = set_nxt(F);
   TB2Args t = tb_args(F, cur, mid, nxt);
-  const int nr = (int)F->tb_ritems.size() / 2;  // R1's order, then R2's (tb_plan)
+  const int nr = (int)F->tb_ritems.size();
   FusedArgs r1 = rim_args(F, fa, cur, mid), r2 = rim_args(F, fa, mid, nxt);
   {  // CUs left free by the two-step launch / the rim launches (A/B; the multi-rank default)
     const int rl = F->res_l >= 0 ? F->res_l : F->tb_res, rr = F->res_r >= 0 ? F->res_r : F->tb_res;
@@ -3442,38 +3412,11 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
   // run on a side stream beside L, taking the CUs L's workgroups leave at the end of its queue
   // (the strips read L's border values of mid and follow L).  One timing span covers L and R1
   const int na = F->tb_r1a && !F->tb_pol ? std::min(F->tb_rs0, nr) : 0;
-  // the two-step items whose footprint meets no rim box (tb_plan puts them first) read only
-  // what the previous pair's two-step kernel wrote and write the buffers its rim launches no
-  // longer read after its first rim launch: they run on a third stream, released at that point
-  // of the previous pair (ev_r1done), beside its second rim launch.  Not with DFT monitors
-  // (their samples of the previous pair read the compact boxes these items rewrite)
-  const int ni = t.n;
-  const int nl = (F->tb_lint && F->dfts.empty() && !F->tb_pol) ? std::min(F->tb_nint, ni) : 0;
   // (the stream-ordering events below release at device scope: every reader is on this device)
-  if ((na > 0 || nl > 0) && !F->s_aux) {
+  if (na > 0 && !F->s_aux) {
     HIPCHK(hipStreamCreateWithFlags(&F->s_aux, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&F->ev_start, hipEventDisableTiming | hipEventReleaseToDevice));
     HIPCHK(hipEventCreateWithFlags(&F->ev_early, hipEventDisableTiming | hipEventReleaseToDevice));
-  }
-  if (nl > 0 && !F->s_lint) {
-    HIPCHK(hipStreamCreateWithFlags(&F->s_lint, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&F->ev_lint, hipEventDisableTiming | hipEventReleaseToDevice));
-    HIPCHK(hipEventCreateWithFlags(&F->ev_r1done, hipEventDisableTiming | hipEventReleaseToDevice));
-  }
-  if (nl > 0) {
-    if (!F->tb_r1done_ok || F->tb_lint == 2)  // no previous pair in this batch: after all before
-      HIPCHK(hipEventRecord(F->ev_r1done, F->stream));
-    HIPCHK(hipStreamWaitEvent(F->s_lint, F->ev_r1done, 0));
-    TB2Args ti = t;
-    ti.n = nl;
-    ti.ctr_line = 6;
-    if (F->tb_lint >= 3) ti.wg_limit = std::max(1, k_cu_count() * F->tb_lint / 8);
-    const int kl = k_tb2(ti, F->s_lint, F->ctr_base);
-    if (kl) return fused_fail("two-step kernel launch failed", kl);
-    HIPCHK(hipEventRecord(F->ev_lint, F->s_lint));
-    t.n = ni - nl;
-    t.items = t.items + nl;
-    if (t.uflag) t.uflag = t.uflag + nl;
   }
   int k = ev_begin(TM_TB);
   int kr = 0;
@@ -3481,7 +3424,7 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
     HIPCHK(hipEventRecord(F->ev_start, F->stream));
     HIPCHK(hipStreamWaitEvent(F->s_aux, F->ev_start, 0));
   }
-  kr = t.n > 0 ? k_tb2(t, F->stream, F->ctr_base) : 0;
+  kr = k_tb2(t, F->stream, F->ctr_base);
   if (kr) return fused_fail("two-step kernel launch failed", kr);
   if (na > 0) {
     kr = k_tile_items(r1, r1.titems, r1.tgeo, r1.tflag, na, 5, F->s_aux, F->ctr_base);
@@ -3493,10 +3436,8 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
       if (kr) return fused_fail("rim kernel launch failed", kr);
     }
     HIPCHK(hipStreamWaitEvent(F->stream, F->ev_early, 0));
-    if (nl > 0) HIPCHK(hipStreamWaitEvent(F->stream, F->ev_lint, 0));
     ev_end(k);
   } else {
-    if (nl > 0) HIPCHK(hipStreamWaitEvent(F->stream, F->ev_lint, 0));
     ev_end(k);
     k = ev_begin(TM_RIM);
     kr = k_tile_items(r1, r1.titems, r1.tgeo, r1.tflag, nr, 4, F->stream, F->ctr_base);
@@ -3512,15 +3453,6 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
   // the step's sources, then the guard of the middle step (its terms' points hold step n+1 in
   // mid: rim items, or the two-step items' store box)
   if (tb_tail(F, s0, mid.D, mid.E, t_mid)) return -1;
-  // the next pair's interior two-step items may start from here: R1, every two-step item of
-  // this pair and the middle step's guard are done, and what follows (R2, source(n+1), the guard
-  // of nxt) reads only points of mid within one cell of the rim and nxt, which those items
-  // neither write nor, beyond the rim's reach, read
-  F->tb_r1done_ok = false;
-  if (nl > 0) {
-    HIPCHK(hipEventRecord(F->ev_r1done, F->stream));
-    F->tb_r1done_ok = true;
-  }
   if (dft_due(F, t_mid)) {  // fields::update_dfts after the pair's first step, from mid
     DevFields fm = F->f;
     for (int d = 0; d < 3; d++)
@@ -3531,8 +3463,7 @@ int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begin, EE 
     if (r) return -1;
   }
   k = ev_begin(TM_RIM);
-  kr = k_tile_items(r2, r2.titems + nr, r2.tgeo + 4 * nr, r2.tflag ? r2.tflag + nr : nullptr, nr,
-                    4, F->stream, F->ctr_base);
+  kr = k_tile_items(r2, r2.titems, r2.tgeo, r2.tflag, nr, 4, F->stream, F->ctr_base);
   ev_end(k);
   if (kr) return fused_fail("rim kernel launch failed", kr);
   if (F->tb_pol) {
@@ -3609,7 +3540,7 @@ int tb_pair_multi(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, EB &ev_begi
   const int cus = k_cu_count();
   const int res = F->tb_res >= 0 ? F->tb_res : TB_RES_CUS;
   t.wg_limit = res > 0 ? cus - res : 0;
-  const int nr = (int)F->tb_ritems.size() / 2, nf = F->tb_rfree;
+  const int nr = (int)F->tb_ritems.size(), nf = F->tb_rfree;
   int k = ev_begin(TM_TB);
   int kr = k_tb2(t, F->stream, F->ctr_base);
   ev_end(k);
@@ -3796,7 +3727,6 @@ int step_batch(mnl_fields *F, int nsteps) {
     ev_end(k);
     return r;
   };
-  F->tb_r1done_ok = false;  // the batch's first pair waits for everything before it
   for (int s0 = 0; s0 < nsteps; s0 += CH) {
     int ns = std::min(CH, nsteps - s0);
     if (!F->dfts.empty() && dft_prepare(F, F->t, ns)) return -1;
@@ -3853,7 +3783,6 @@ int step_batch(mnl_fields *F, int nsteps) {
         if (post_step(s, 1)) return -1;  // DFT of the pair's second step (the new state)
         continue;
       }
-      F->tb_r1done_ok = false;  // a one-step step: the next pair waits for everything before
       if (tb_chain_join(F)) return -1;
       if (F->fused && F->nranks > 1) {
         if (step_fused_multi(F, sD, ev_begin, ev_end) || post_step(s)) return -1;
@@ -4152,7 +4081,6 @@ int nan_result(mnl_fields *F) {
       if (x >= 0 && (bad_t < 0 || (long long)x < bad_t)) bad_t = (long long)x;
   }
   if (bad_t < 0) return 0;
-  F->nan_bad_t = bad_t;
   return fail("simulation fields are NaN or Inf (at time step " + std::to_string(bad_t) +
               "; fields left at time step " + std::to_string(F->t) + ")");
 }
@@ -4347,14 +4275,10 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
   if (const char *tz = getenv("MNL_TB_ZCHUNK"))
     F->tb_zchunk = std::max(0, atoi(tz)), F->tb_zchunk_env = true;
   if (const char *tn = getenv("MNL_TB_NARROW")) F->tb_narrow = atoi(tn) != 0;
-  if (const char *tx = getenv("MNL_TB_PX")) F->tb_px = atoi(tx) == 1 ? 1 : 2;
   if (const char *tq = getenv("MNL_TB_POL")) F->tb_pol_on = atoi(tq) != 0;
   if (const char *ta = getenv("MNL_TB_R1A")) F->tb_r1a = atoi(ta) != 0;
-  if (const char *tl = getenv("MNL_TB_LINT")) F->tb_lint = atoi(tl);
   if (const char *ef = getenv("MNL_EV_FENCE")) F->ev_fence = atoi(ef) != 0;
   if (const char *sg = getenv("MNL_TB_SRCGUARD")) F->tb_srcguard = atoi(sg) != 0;
-  if (const char *sz = getenv("MNL_TB_STRIP_ZCHUNK")) F->tb_szc = std::max(0, atoi(sz));
-  if (const char *tp = getenv("MNL_TB_R2LPT")) F->tb_r2lpt = std::max(0, std::min(2, atoi(tp)));
   if (const char *to = getenv("MNL_TB_OOM")) F->tb_oom_test = atoi(to) != 0;
   if (const char *dp = getenv("MNL_DFT_PAL")) F->dft_pal = atoi(dp) != 0;
   if (const char *dc = getenv("MNL_DFT_CMP")) F->dft_cmp = atoi(dc) != 0;
@@ -5548,18 +5472,6 @@ int mnl_fields_set_schedule(mnl_fields *F, int which, int value) {
   } else if (which == 16) {  // a pair's source + guard launches merged (one rank)
     F->tb_srcguard = v;
     return 0;
-  } else if (which == 15) {  // planes per narrow strip item (0: the rim's chunk length)
-    if (value < 0 || value > FUSED_MAXCH) return fail("bad strip chunk");
-    F->tb_szc = value;
-  } else if (which == 14) {  // the second rim launch's order (one rank): 1 longest first,
-    if (value < 0 || value > 2) return fail("bad rim order");  // 2 the narrow strips first
-    F->tb_r2lpt = value;
-  } else if (which == 13) {  // interior two-step items beside the previous pair's R2
-    if (value < 0 || value > 7) return fail("bad interior-items setting");
-    F->tb_lint = value;  // (2: split, released after all before; 3..7: on 3/8..7/8 of the CUs)
-  } else if (which == 10) {  // columns per lane of the two-step kernel (1: round-5 kernel)
-    if (value != 1 && value != 2) return fail("bad two-step layout");
-    F->tb_px = value;
   } else if (which == 9) {  // most own columns of a two-step item (0: TB_OXW = 124)
     if (value != 0 && (value < 4 || value > TB_OXW)) return fail("bad two-step width");
     F->tb_ox = value;
@@ -5582,23 +5494,22 @@ int mnl_fields_set_schedule(mnl_fields *F, int which, int value) {
 
 int mnl_fields_tb_info(mnl_fields *F, double *out, int n) {
   if (!F || !out || n < 1) return fail("bad argument");
-  const double v[15] = {F->fused && F->tb_have && F->tb_enabled && F->tb_last ? 1.0 : 0.0,
+  const double v[14] = {F->fused && F->tb_have && F->tb_enabled && F->tb_last ? 1.0 : 0.0,
                        F->tb_cells,
                        F->tb_border,
                        F->tb_cells_nu,
                        F->rim_cells,
                        F->rim_cells_nu,
                        double(F->tb_items.size()),
-                       double(F->tb_ritems.size() / 2),
+                       double(F->tb_ritems.size()),
                        F->tb_items.empty() ? 0.0 : double((F->tb_items[0].z >> 16) -
                                                           (F->tb_items[0].z & 0xFFFF)),
                        double(F->tb_nnarrow),
                        F->tb_enabled ? 1.0 : 0.0,
                        double(F->tb_zchunk),  // the setting (0: automatic)
                        double(F->tb_ox ? F->tb_ox : TB_OXW),  // most own columns of an item
-                       F->tb_pol ? 1.0 : 0.0,  // polarization chunks stepped inside the pairs
-                       double(F->tb_nint)};  // interior two-step items (first in the list)
-  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
+                       F->tb_pol ? 1.0 : 0.0};  // polarization chunks stepped inside the pairs
+  for (int i = 0; i < n && i < 14; i++) out[i] = v[i];
   return 0;
 }
 

@@ -317,8 +317,6 @@ struct mnl_fields {
   hipStream_t s_aux = nullptr, s_comm = nullptr;
   hipEvent_t ev_start = nullptr, ev_early = nullptr, ev_x1 = nullptr, ev_shell = nullptr,
              ev_x0 = nullptr;
-  hipStream_t s_lint = nullptr;     // pairs: interior two-step items (tb_lint)
-  hipEvent_t ev_lint = nullptr, ev_r1done = nullptr;
   double *pp_B[3] = {nullptr, nullptr, nullptr}, *pp_D[3] = {nullptr, nullptr, nullptr};
   double *pp_E[3] = {nullptr, nullptr, nullptr}, *pp_H[3] = {nullptr, nullptr, nullptr};
   double *pp_UB[3] = {nullptr, nullptr, nullptr};
@@ -369,22 +367,11 @@ struct mnl_fields {
   bool tb_r1a = true;               // MNL_TB_R1A=0 / set_schedule 12: R1 after the two-step
                                     // kernel instead of its non-strip items beside it
   int tb_rs0 = 0;                   // rim items before the narrow strips (one rank)
-  int tb_lint = 0;                  // MNL_TB_LINT=1 / set_schedule 13: the interior two-step
-                                    // items beside the previous pair's second rim launch
-  int tb_nint = 0;                  // two-step items whose footprint meets no rim box (first)
   bool ev_fence = false;            // MNL_EV_FENCE=1: timing events with the default fence
   bool tb_srcguard = true;          // MNL_TB_SRCGUARD=0 / set_schedule 16: a pair's sources
                                     // and guard as two launches per step (default: one)
-  int tb_szc = 0;                   // planes per narrow strip item (0: the rim's chunk length;
-                                    // MNL_TB_STRIP_ZCHUNK / set_schedule 15)
-  int tb_r2lpt = 0;                 // MNL_TB_R2LPT / set_schedule 14: the second rim launch
-                                    // longest first (1) or strips first (2); default: the
-                                    // first one's order, narrow strips last
-  bool tb_r1done_ok = false;        // ev_r1done marks the previous pair's R1 join (same batch)
   bool tb_pol = false;              // the pairs step polarization chunks (general kernel, one
                                     // step at a time beside the rim launches; one rank)
-  int tb_px = 2;                    // columns per lane of the two-step kernel (1: the round-5
-                                    // kernel, for A/B; MNL_TB_PX)
   bool tb_ox_set = false;           // tb_ox set by set_schedule (the tuner keeps it)
   int tb_ox = 0;                    // most own columns of a two-step item (0: TB_OXW = 124,
                                     // the 128 columns of lanes less two halo columns per side)
@@ -421,7 +408,6 @@ struct mnl_fields {
   double rim_cells = 0, rim_lean = 0, rim_cells_nu = 0;  // rim items: own / lean / mixed cells
   int nan_every = 1;                // NaN guard cadence (src/step.cpp:138-139: every step)
   int since_nan = 0;                // steps since the last NaN guard (across calls)
-  long long nan_bad_t = -1;         // first failing step of the last tripped NaN guard (-1: none)
   bool nan_due = false;             // a guard is due once the state is complete (pending rim)
   int nan_launched = 0;             // guards launched in this chunk (flag read at its end)
   long long nan_at = 0;             // time step of the state the next guard checks
@@ -483,10 +469,9 @@ struct mnl_fields {
                     (void *)d_tb_items})
       if (p) hipFree(p);
     comm.reset();
-    for (hipEvent_t e : {ev_start, ev_early, ev_x1, ev_shell, ev_x0, ev_lint, ev_r1done})
+    for (hipEvent_t e : {ev_start, ev_early, ev_x1, ev_shell, ev_x0})
       if (e) hipEventDestroy(e);
     if (s_aux) hipStreamDestroy(s_aux);
-    if (s_lint) hipStreamDestroy(s_lint);
     if (s_comm) hipStreamDestroy(s_comm);
     if (stream) hipStreamDestroy(stream);
   }

@@ -405,7 +405,6 @@ struct TB2Args {
   ItemClock clk;                // diagnostics: per-item start / end times (clk.rec null: off)
   int ncmp;                     // DFT compact boxes
   TBCmp cmp[TB_MAXCMP];
-  int px;                       // columns per lane: 2 (round 6), 1 (the round-5 kernel, A/B)
 };
 // NaN guard of fields::step (src/step.cpp:138-139): get_field(D_EnergyDensity, gv.center())
 // = 1/2 sum_d E_d(c) D_d(c), each value the interpolation of src/monitor.cpp:127-160 over

@@ -81,34 +81,61 @@ def oracle_tb():
 @pytest.mark.parametrize("schedule", [(("rim_zchunk", 12),), (("res", 16),), (("res_rim", 40),),
                                       (("res_tb2", 24), ("narrow", 0)), (("tb_ox", 60),),
                                       (("tb_ox", 60), ("tb_zchunk", 5)), (("tb_ox", 37),),
-                                      (("tb_ox", 9), ("tb_zchunk", 3)), (("tb_px", 1),),
-                                      (("tb_px", 1), ("tb_ox", 60))],
+                                      (("tb_ox", 9), ("tb_zchunk", 3))],
                          ids=["rim_zchunk12", "res16", "res_rim40", "res_tb2_24_wide", "ox60",
-                              "ox60_z5", "ox37_odd_starts", "ox9_z3", "px1", "px1_ox60"])
+                              "ox60_z5", "ox37_odd_starts", "ox9_z3"])
 def test_tb_schedule_options_bitwise(oracle_tb, schedule):
     """The scheduling options of Fields.set_schedule (rim item length, CUs left free by the
     pair launches, the strip body, two-step item widths -- 37 columns puts every other item's
     first column on an odd x (lane 0 three columns left of it, own ranges that start and end
     inside a lane's column pair: the 8-byte store paths), 9 columns many ragged items -- short
-    two-step chunks, the round-5 one-column-per-lane kernel) change only how the same per-point
-    arithmetic is laid out: bitwise the oracle."""
+    two-step chunks) change only how the same per-point arithmetic is laid out: bitwise the
+    oracle."""
     p = sc_tb(ProductSim, profile=True, schedule=schedule)
     assert p._fields().tb_info()["active"] and p._fields().kernel_stats(5)[0] >= 4
     _same(p, oracle_tb)
 
 
 def test_tb_interior_items_beside_previous_rim():
-    """Narrow, short two-step items (9 columns, 3 planes): many have a footprint that meets no
-    rim box, and one rank runs those on a third stream from the previous pair's middle guard on,
-    beside its second rim launch (tb_lint).  Long batches of pairs, odd calls and a one-step
-    step between them: bitwise the oracle and the same run with the option off."""
+    """Narrow, short two-step items (9 columns, 3 planes), many of them with a footprint that
+    meets no rim box, in the default schedule.  Long batches of pairs, odd calls and a one-step
+    step between them: bitwise the oracle and the same run stepped one step at a time."""
     sched = (("tb_ox", 9), ("tb_zchunk", 3))
     steps = (1, 24, 3, 1, 10)
-    p = sc_tb(ProductSim, profile=True, schedule=sched + (("tb_lint", 1),), steps=steps)
+    p = sc_tb(ProductSim, profile=True, schedule=sched, steps=steps)
     info = p._fields().tb_info()
-    assert info["active"] and 0 < info["tb_interior_items"] < info["tb_items"], info
+    assert info["active"] and info["tb_items"] > 0 and p._fields().kernel_stats(5)[0] >= 4, info
     _same(p, sc_tb(make_oracle, steps=steps))
-    _same(p, sc_tb(ProductSim, schedule=sched, steps=steps))
+    q = sc_tb(ProductSim, tb=False, schedule=sched, steps=steps)
+    assert not q._fields().tb_info()["active"]
+    _same(p, q)
+
+
+RETIRED = {"tb_px": 10, "tb_lint": 13, "r2_lpt": 14, "strip_zchunk": 15}
+# every surviving option with its default value (the run stays the default schedule)
+SURVIVING = {"narrow": 1, "dft_pal": 1, "res": -1, "res_tb2": -1, "res_rim": -1, "dft_cmp": 1,
+             "rim_zchunk": 0, "nr_early": 1, "tb_zchunk": 0, "tb_ox": 0, "tb_pol": 1,
+             "r1_beside": 1, "src_guard": 1}
+
+
+def test_retired_schedule_options_rejected(oracle_tb):
+    """The schedule variants removed after round 6: their names raise,
+    their numbers fail as any unknown number does and change nothing (the run stays bitwise the
+    oracle); every surviving name is still accepted."""
+    from meep_nl_amd._lib import lib
+    p = sc_tb(ProductSim, steps=())
+    f = p._fields()
+    for name, num in RETIRED.items():
+        with pytest.raises(KeyError):
+            f.set_schedule(name, 1)
+        assert lib().mnl_fields_set_schedule(f.h, num, 1) != 0
+        assert b"bad schedule option" in lib().mnl_last_error()
+    for name, val in SURVIVING.items():
+        f.set_schedule(name, val)
+    for n in (1, 10):
+        p.step(n)
+    assert f.tb_info()["active"]
+    _same(p, oracle_tb)
 
 
 def sc_tb_volume(make, big, steps=(1, 10, 1, 6), schedule=()):

@@ -50,27 +50,11 @@ def kind(name):
     return None
 
 
-def merge(a, b):
-    """two tb2_kernel dispatches of one pair (the interior items on their own stream, then the
-    others): bytes add up, the span is their union"""
-    m = dict(a)
-    if "bytes" in a:
-        m["bytes"] = a["bytes"] + b["bytes"]
-    if "start" in a:
-        m["start"], m["end"] = min(a["start"], b["start"]), max(a["end"], b["end"])
-        m["busy"] = a.get("busy", a["end"] - a["start"]) + (b["end"] - b["start"])
-    return m
-
-
 def per_pair(disp):
-    """dispatch list [(id, kind, value...)] in dispatch order -> list of (tb2, [tile, ...]);
-    consecutive tb2_kernel dispatches belong to one pair"""
+    """dispatch list [(id, kind, value...)] in dispatch order -> list of (tb2, [tile, ...])"""
     pairs, cur = [], None
     for d in disp:
         if d["kind"] == "tb2":
-            if cur and not cur["tile"]:
-                cur["tb2"] = merge(cur["tb2"], d)
-                continue
             if cur:
                 pairs.append(cur)
             cur = {"tb2": d, "tile": []}
@@ -114,7 +98,7 @@ def main():
     tpairs = [p for p in per_pair(tr) if len(p["tile"]) >= 2][1:]
     span = [(max([p["tb2"]["end"]] + [t["end"] for t in p["tile"]]) - p["tb2"]["start"]) / 1e6
             for p in tpairs]
-    tb2_ms = [p["tb2"].get("busy", p["tb2"]["end"] - p["tb2"]["start"]) / 1e6 for p in tpairs]
+    tb2_ms = [(p["tb2"]["end"] - p["tb2"]["start"]) / 1e6 for p in tpairs]
     last_rim_ms = [(p["tile"][-1]["end"] - p["tile"][-1]["start"]) / 1e6 for p in tpairs]
     rd = [p for p in counter_pairs(a.fetch, "FETCH_SIZE", 2048.0) if len(p["tile"]) >= 2][1:]
     wr = [p for p in counter_pairs(a.write, "WRITE_SIZE", 1024.0) if len(p["tile"]) >= 2][1:]
