@@ -248,7 +248,7 @@ int mnl_fields_step(mnl_fields *f, int nsteps);
  * and one with 2 * reps timed steps).  A run is two warm-up steps and r timed ones, r = reps
  * rounded up to even.  Advances the fields by at most 2 + 51 * (2 + r) + 4 * (2 + 2 * reps)
  * steps (112 + 59 * reps for even reps), with results identical to plain stepping.  *zchunk = the length kept (0 = automatic), *gen_cus = the
- * CUs kept (0 = one launch after the other); -1 = not tuned (not in the fused tile mode:
+ * CUs kept (0 = one launch after the other); -1 = not tuned (not in the fused mode:
  * at most 2 steps taken). */
 int mnl_fields_tune(mnl_fields *f, int reps, int *zchunk, int *gen_cus);
 int mnl_fields_set_nan_check(mnl_fields *f, int every);
@@ -345,7 +345,8 @@ int mnl_fields_set_fused(mnl_fields *f, int allow);
 /* bit 0: the last step ran the fused interior kernel; bit 1: it read chi1inv
  * through the palette (DESIGN.md "chi1inv palette"); bit 2: field arrays are
  * requested physically contiguous; bit 4: the fused step ran as the single tile
- * kernel (lean + PML bodies); bits 8-15: how many
+ * kernel (lean + PML bodies), which is the only fused step there
+ * is: set whenever bit 0 is; bits 8-15: how many
  * contiguity requests the driver could not satisfy (plain allocations instead). */
 int mnl_fields_mode(mnl_fields *f, int *fused);
 /* Enable HIP-event timing around every sub-step kernel group (on the stream
@@ -353,9 +354,9 @@ int mnl_fields_mode(mnl_fields *f, int *fused);
 int mnl_fields_set_profiling(mnl_fields *f, int on);
 /* Accumulated launches / total ms of the dominant interior kernel since the
  * last mnl_fields_set_profiling, and its algorithmic bytes per launch.
- * which = 0: fused step kernel (fused mode) or curl B = step_db(B_stuff);
+ * which = 0: the tile kernel (fused mode) or curl B = step_db(B_stuff);
  * which = 1: curl D = step_db(D_stuff) (unfused mode);
- * which = 2: general fused kernel (PML / boundary tiles);
+ * which = 2: general fused kernel (the polarization chunks);
  * which = 3: the DFT updates of one step (all flux objects);
  * which = 4: the E update (update_eh(E_stuff): chi(2) Newton-Raphson,
  *            Lorentzian P), unfused mode; bytes 0 (not HBM-bound);

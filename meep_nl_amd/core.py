@@ -407,7 +407,7 @@ class Fields:
         backward) and the three best again with 2 * reps timed steps, one for one-step
         stepping and one more with 2 * reps.  At most 2 + 51 * (2 + r) + 4 * (2 + 2 * reps)
         steps (112 + 59 * reps for even reps), results identical to plain stepping (round 6: 8 timed steps by default, 4 gave choices off by up to 10 %
-        at 256^3).  Returns (zchunk, gen_cus); -1 = not tuned (not in the fused tile mode)."""
+        at 256^3).  Returns (zchunk, gen_cus); -1 = not tuned (not in the fused mode)."""
         z, g = ctypes.c_int(0), ctypes.c_int(0)
         check(lib().mnl_fields_tune(self.h, int(reps), ctypes.byref(z), ctypes.byref(g)))
         return z.value, g.value
@@ -542,14 +542,15 @@ class Fields:
         return bool(v.value & 1)
 
     def tile_mode(self):
-        """True if the fused step runs as one tile kernel (lean + PML bodies)."""
+        """True if the fused step runs as one tile kernel (lean + PML bodies): always, in the
+        fused mode (it is the only fused step)."""
         v = ctypes.c_int()
         check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
         return bool(v.value & 16)
 
     def fused_concurrent(self):
         """True if the last fused step ran the polarization chunks' general kernel beside the
-        tile (or lean) kernel on a CU split: kernel_stats(0) then spans both launches."""
+        tile kernel on a CU split: kernel_stats(0) then spans both launches."""
         v = ctypes.c_int()
         check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
         return bool(v.value & 32)

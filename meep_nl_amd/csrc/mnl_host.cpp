@@ -1342,7 +1342,7 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
 // with an upper neighbour (its D needs the neighbour's new B first); that
 // plane is the shell, stepped by the shell kernels around the halo exchange.
 // L = interior box (no PML chunk along any direction) within [1, N-2]: tiles
-// whose whole footprint lies in L run the lean kernel.
+// whose whole footprint lies in L run the lean body.
 static void split_range(std::vector<int> &b, int lo, int hi_excl, int step, int align) {
   // append starts covering [lo, hi_excl) in pieces of at most `step`, starts aligned
   int x = lo;
@@ -1354,18 +1354,6 @@ static void split_range(std::vector<int> &b, int lo, int hi_excl, int step, int 
   }
 }
 
-// general tiles read the lean kernel's B_new on their halo (default); MNL_LEAN_HALO=0
-// recomputes it
-static int lean_halo_reads(const mnl_fields *F) { return F->lean_halo ? 1 : 0; }
-
-// Tile mode.  Tiles of the lean body's shape over all of G:
-// columns in pieces of <= 64 from G.lo (128-byte aligned), rows in balanced pieces of
-// <= 14, z chunks; every chunk whose footprint (planes zs-1 .. ze) misses the
-// polarization boxes' z range is stepped by the tile kernel, one item per (tile, chunk),
-// with the body its footprint needs (lean inside L, else the PML body of the directions
-// whose tables are not the identity there).  The remaining (polarization) chunks keep the
-// general kernel's items (wide tiles).  Multi-rank: chunk 0 = planes 0..1 (the B the
-// lower neighbour needs), launched first.
 // directions whose PML tables are not the identity somewhere in [lo, hi] (per axis)
 int pml_dirs_in(const mnl_fields *F, const int lo[3], const int hi[3]) {
   const DevGrid &g = F->g;
@@ -1428,9 +1416,32 @@ int strip_item_code(const mnl_fields *F, const FusedArgs &a, int x0, int x1, int
   return (1 << 24) | (1 << 29) | (1 << 30);
 }
 
-bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
+// Fused geometry.  Tiles of the lean body's shape over all of G:
+// columns in pieces of <= 64 from G.lo (128-byte aligned), rows in balanced pieces of
+// <= 14, z chunks; every chunk whose footprint (planes zs-1 .. ze) misses the
+// polarization boxes' z range is stepped by the tile kernel, one item per (tile, chunk),
+// with the body its footprint needs (lean inside L, else the PML body of the directions
+// whose tables are not the identity there).  The remaining (polarization) chunks keep the
+// general kernel's items (wide tiles).  Multi-rank: chunk 0 = planes 0..1 (the B the
+// lower neighbour needs), launched first.
+bool make_fused_boxes(mnl_fields *F) {
   const DevGrid &g = F->g;
+  Box G, L;
+  for (int k = 0; k < 3; k++) {
+    G.lo[k] = 0;
+    G.hi[k] = g.N[k] - 2;
+    if (G.hi[k] < G.lo[k]) return false;
+    L.lo[k] = std::max(F->interior.lo[k], 1);
+    L.hi[k] = std::min(F->interior.hi[k], g.N[k] - 2);
+  }
+  if (F->interior.hi[0] < F->interior.lo[0])
+    for (int k = 0; k < 3; k++) L.lo[k] = 1, L.hi[k] = 0;
+  F->fusedG = G;
+  F->fusedL = L;
   FusedArgs &a = F->fgeo;
+  memset(&a, 0, sizeof(a));
+  a.G = G;
+  a.L = L;
   std::vector<int> xb, yb, zb, gyb;
   split_range(xb, G.lo[0], G.hi[0] + 1, FX_HOST, 16);
   {
@@ -1518,7 +1529,6 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
   a.nx = (int)xb.size();
   a.ny = (int)yb.size();
   a.ngy = (int)gyb.size();
-  a.nny = 0;
   a.nch = (int)zb.size();
   for (size_t i = 0; i < xb.size(); i++) a.xb[i] = xb[i];
   a.xb[xb.size()] = G.hi[0] + 1;
@@ -1526,10 +1536,8 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
   a.yb[yb.size()] = G.hi[1] + 1;
   for (size_t i = 0; i < gyb.size(); i++) a.gyb[i] = gyb[i];
   a.gyb[gyb.size()] = G.hi[1] + 1;
-  a.nyb[0] = G.lo[1], a.nyb[1] = G.hi[1] + 1;
   for (size_t i = 0; i < zb.size(); i++) a.zb[i] = zb[i];
   a.zb[zb.size()] = G.hi[2] + 1;
-  a.lx0 = 0, a.lx1 = -1, a.ly0 = 0, a.ly1 = -1, a.nlzr = 0;  // no lean-only launch
   for (int k = 0; k < 3; k++) {
     a.N[k] = g.N[k];
     a.off[k] = g.off[k];
@@ -1538,11 +1546,10 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
     a.oun_lo[k] = g.owned_lo_un[k];
     a.oun_hi[k] = std::min(g.owned_hi_un[k], G.hi[k]);
   }
-  auto pml_dirs = [&](const int lo[3], const int hi[3]) { return pml_dirs_in(F, lo, hi); };
   // ---- tile items
   F->titems.clear();
   F->gitems.clear();
-  F->tile_cells = F->lean_cells = F->gen_cells = 0;
+  F->tile_cells = F->gen_cells = 0;
   F->tile_z.assign(std::max(g.N[2], 1), 0);
   std::vector<int> early, heavy, lean, gen_e, gen_r;
   for (int ch = 0; ch < a.nch; ch++) {
@@ -1553,7 +1560,7 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
           const int y0 = a.gyb[ty] - 1;
           const int lo[3] = {a.xb[tx] - 1, y0, zs - 1};
           const int hi[3] = {a.xb[tx] + FX_HOST, y0 + FUSED_GW_ROWS + 1, ze + 1};
-          const int m = pml_dirs(lo, hi);
+          const int m = pml_dirs_in(F, lo, hi);
           const int v = tx | (ty << 8) | (ch << 16) |
                         (((m & ~2) == 0 ? 2 : (m & ~4) == 0 ? 4 : 7) << 24);
           F->gen_cells += (long long)(a.xb[tx + 1] - a.xb[tx]) * (a.gyb[ty + 1] - a.gyb[ty]) *
@@ -1570,7 +1577,6 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
         F->tile_cells += cells;
         bool in_l;
         const int code = tile_item_code(F, a, L, x0, x1, y0, y1, zs, ze, &in_l);
-        if (in_l) F->lean_cells += cells;
         const int body = (code >> 24) & 7;
         const int v = tx | (ty << 8) | (ch << 16) | code;
         if (F->tile_body_mask >= 0 && !((F->tile_body_mask >> body) & 1)) continue;  // timing only
@@ -1609,270 +1615,6 @@ bool make_tile_boxes(mnl_fields *F, const Box &G, const Box &L) {
   F->gitems.insert(F->gitems.end(), gen_r.begin(), gen_r.end());
   a.ngen = (int)F->gitems.size();
   a.ngen_e = (int)gen_e.size();
-  a.ngen_n = a.ngen_ne = 0;
-  // ---- shell: the top plane of a rank with an upper neighbour
-  BoxList &bl = F->fused_shell;
-  memset(&bl, 0, sizeof(bl));
-  if (F->nranks > 1 && F->rank + 1 < F->nranks) {
-    Box b;
-    for (int k = 0; k < 3; k++) b.lo[k] = 0, b.hi[k] = g.N[k] - 1;
-    b.lo[2] = b.hi[2] = g.N[2] - 1;
-    bl.b[0] = b;
-    bl.start[0] = 0;
-    bl.start[1] = (long long)g.N[0] * g.N[1];
-    bl.n = 1;
-  }
-  return true;
-}
-
-bool make_fused_boxes(mnl_fields *F) {
-  const DevGrid &g = F->g;
-  Box G, L;
-  for (int k = 0; k < 3; k++) {
-    G.lo[k] = 0;
-    G.hi[k] = g.N[k] - 2;
-    if (G.hi[k] < G.lo[k]) return false;
-    L.lo[k] = std::max(F->interior.lo[k], 1);
-    L.hi[k] = std::min(F->interior.hi[k], g.N[k] - 2);
-  }
-  if (F->interior.hi[0] < F->interior.lo[0])
-    for (int k = 0; k < 3; k++) L.lo[k] = 1, L.hi[k] = 0;
-  F->fusedG = G;
-  F->fusedL = L;
-  FusedArgs &a = F->fgeo;
-  memset(&a, 0, sizeof(a));
-  a.G = G;
-  a.L = L;
-  if (F->tile_mode) return make_tile_boxes(F, G, L);
-  // z-chunk: MNL_FUSED_ZCHUNK, else chosen below (after the lean geometry is known) so
-  // that the lean items fill whole rounds of one workgroup per CU; 512^3 gets 24 planes
-  // (measured 3.13 ms/step vs 3.17 (16) and 3.27 (32), profiles/README.md)
-  int zc = std::min(F->fused_zchunk > 0 ? F->fused_zchunk : 24, FUSED_MAXCH);
-  // ---- x tiles (<= 64 columns, starts on 16-double = 128-byte boundaries).  Lean
-  // tiles store columns [lx_first, x_end]: footprint x0-1 .. x1+1 inside L (the
-  // lanes past x1 load but only feed values that are never stored).
-  std::vector<int> xb;
-  const int lx_first = (L.lo[0] + 1 + 15) / 16 * 16;
-  const int x_end = (L.hi[0] / 16) * 16 - 1;
-  const int ly_first = L.lo[1] + 1, y_end = L.hi[1] - 1;
-  // z segments: lean chunks need planes zs-1 .. ze inside L and away from the
-  // polarization box (where E is stored and P updated: general kernels only)
-  const int lz_first = L.lo[2] + 1;
-  std::vector<std::pair<int, int>> lean_seg;  // [zs, ze) ranges of lean planes
-  {
-    int pzl = INT32_MAX, pzh = -1;
-    for (int k = 0; k < F->f.npol; k++)
-      if (F->f.pol[k].nz.lo[2] <= F->f.pol[k].nz.hi[2]) {
-        pzl = std::min(pzl, F->f.pol[k].nz.lo[2]);
-        pzh = std::max(pzh, F->f.pol[k].nz.hi[2]);
-      }
-    auto add = [&](int a0, int a1) {
-      if (a1 > a0) lean_seg.push_back({a0, a1});
-    };
-    if (pzh < 0) {
-      add(lz_first, L.hi[2]);
-    } else {
-      add(lz_first, std::min(L.hi[2], pzl - 1));
-      add(std::max(lz_first, pzh + 2), L.hi[2]);
-    }
-  }
-  const bool anylean = x_end >= lx_first && y_end >= ly_first && !lean_seg.empty();
-  if (anylean && F->fused_zchunk <= 0) {
-    // score = (items / whole rounds of items) x (planes / (planes + the halo plane))
-    std::vector<int> tx;
-    split_range(tx, lx_first, x_end + 1, FX_HOST, 16);
-    const long long ntile = (long long)tx.size() * ((y_end - ly_first + 14) / 14);
-    const long long cus = std::max(1, k_cu_count());
-    double best = -1;
-    for (int cand : {12, 14, 16, 18, 20, 22, 24, 28, 32}) {
-      long long nch = 0, planes = 0;
-      for (auto &sg : lean_seg) {
-        nch += (sg.second - sg.first + cand - 1) / cand;
-        planes += sg.second - sg.first;
-      }
-      const long long items = ntile * nch;
-      const double fill = double(items) / double(((items + cus - 1) / cus) * cus);
-      const double per = double(planes) / double(nch);
-      const double score = fill * per / (per + 1.0);
-      if (score >= best - 1e-12) best = score, zc = cand;  // ties: the longer chunk
-    }
-  }
-  std::vector<int> yb, gyb, zb;
-  const int gstep = FUSED_GW_ROWS;  // general wide-tile rows
-  int gly0 = -1, gly1 = -2;  // general row tiles inside the lean row range
-  if (!anylean) {
-    split_range(xb, G.lo[0], G.hi[0] + 1, FX_HOST, 16);
-    a.lx0 = 0, a.lx1 = -1;
-    yb.push_back(0);
-    a.ly0 = 0, a.ly1 = -1;
-    split_range(gyb, G.lo[1], G.hi[1] + 1, gstep, 1);
-    split_range(zb, G.lo[2], G.hi[2] + 1, zc, 1);
-    a.nlzr = 0;
-  } else {
-    split_range(xb, G.lo[0], lx_first, FX_HOST, 16);
-    a.lx0 = (int)xb.size();
-    split_range(xb, lx_first, x_end + 1, FX_HOST, 16);
-    a.lx1 = (int)xb.size() - 1;
-    split_range(xb, x_end + 1, G.hi[0] + 1, FX_HOST, 16);
-    // lean row tiles: 14 own rows (the last may be shorter), rows y0-1 .. y1+1 inside L
-    split_range(yb, ly_first, y_end + 1, 14, 1);
-    a.ly0 = 0, a.ly1 = (int)yb.size() - 1;
-    yb.push_back(y_end + 1);
-    split_range(gyb, G.lo[1], ly_first, gstep, 1);
-    gly0 = (int)gyb.size();
-    split_range(gyb, ly_first, y_end + 1, gstep, 1);
-    gly1 = (int)gyb.size() - 1;
-    split_range(gyb, y_end + 1, G.hi[1] + 1, gstep, 1);
-    // z chunks: general between the lean segments
-    a.nlzr = 0;
-    int z = G.lo[2];
-    for (auto &sg : lean_seg) {
-      split_range(zb, z, sg.first, zc, 1);
-      a.lzr[a.nlzr][0] = (int)zb.size();
-      split_range(zb, sg.first, sg.second, zc, 1);
-      a.lzr[a.nlzr][1] = (int)zb.size() - 1;
-      a.nlzr++;
-      z = sg.second;
-    }
-    split_range(zb, z, G.hi[2] + 1, zc, 1);
-  }
-  // narrow (16-column) general tiles take rows in tiles of FUSED_GN_ROWS
-  std::vector<int> nyb;
-  split_range(nyb, G.lo[1], G.hi[1] + 1, FUSED_GN_ROWS, 1);
-  if ((int)xb.size() > FUSED_MAXX || (int)yb.size() > FUSED_MAXY + 1 ||
-      (int)gyb.size() > FUSED_MAXGY || (int)nyb.size() > FUSED_MAXNY ||
-      (int)zb.size() > FUSED_MAXZ)
-    return false;
-  a.nx = (int)xb.size();
-  a.ny = (int)yb.size() - 1;
-  a.ngy = (int)gyb.size();
-  a.nny = (int)nyb.size();
-  a.nch = (int)zb.size();
-  for (size_t i = 0; i < xb.size(); i++) a.xb[i] = xb[i];
-  a.xb[xb.size()] = G.hi[0] + 1;
-  for (size_t i = 0; i < yb.size(); i++) a.yb[i] = yb[i];
-  for (size_t i = 0; i < gyb.size(); i++) a.gyb[i] = gyb[i];
-  a.gyb[gyb.size()] = G.hi[1] + 1;
-  for (size_t i = 0; i < nyb.size(); i++) a.nyb[i] = nyb[i];
-  a.nyb[nyb.size()] = G.hi[1] + 1;
-  for (size_t i = 0; i < zb.size(); i++) a.zb[i] = zb[i];
-  a.zb[zb.size()] = G.hi[2] + 1;
-  // ---- general items (chunk-major, then rows, then columns) and cell counts:
-  // wide tiles first, then the 16-column tiles
-  F->gitems.clear();
-  F->lean_cells = F->gen_cells = 0;
-  std::vector<int> narrow;
-  auto lean_ch = [&](int ch) {
-    for (int r = 0; r < a.nlzr; r++)
-      if (ch >= a.lzr[r][0] && ch <= a.lzr[r][1]) return true;
-    return false;
-  };
-  auto narrow_tx = [&](int tx) {
-    return a.xb[tx + 1] - a.xb[tx] <= 16 && (tx < a.lx0 || tx > a.lx1);
-  };
-  for (int ch = 0; ch < a.nch; ch++) {
-    const long long nz = a.zb[ch + 1] - a.zb[ch];
-    for (int ty = 0; ty < a.ngy; ty++)
-      for (int tx = 0; tx < a.nx; tx++) {
-        const int wx = a.xb[tx + 1] - a.xb[tx];
-        if (narrow_tx(tx)) continue;
-        const long long cells = (long long)wx * (a.gyb[ty + 1] - a.gyb[ty]) * nz;
-        const bool lean = tx >= a.lx0 && tx <= a.lx1 && lean_ch(ch) && ty >= gly0 &&
-                          ty <= gly1;
-        if (lean) {
-          F->lean_cells += cells;
-          continue;
-        }
-        F->gen_cells += cells;
-        F->gitems.push_back(tx | (ty << 8) | (ch << 16));
-      }
-    for (int ty = 0; ty < a.nny; ty++)
-      for (int tx = 0; tx < a.nx; tx++) {
-        const int wx = a.xb[tx + 1] - a.xb[tx];
-        if (!narrow_tx(tx)) continue;
-        F->gen_cells += (long long)wx * (a.nyb[ty + 1] - a.nyb[ty]) * nz;
-        narrow.push_back(tx | (ty << 8) | (ch << 16));
-      }
-  }
-  // bits 24-26 of an item: the directions along which its footprint (the
-  // positions whose PML tables the kernel reads) meets a PML chunk or any
-  // non-identity coefficient; the kernel picks a body with the others fixed
-  auto pml_dirs = [&](int v, bool nar) -> int {
-    const int tx = v & 255, ty = (v >> 8) & 255, ch = (v >> 16) & 255;
-    const int TXn = nar ? 16 : 64, R = nar ? (FUSED_GN_ROWS + 1) : (FUSED_GW_ROWS + 1);
-    const int y0 = (nar ? a.nyb[ty] : a.gyb[ty]) - 1;
-    const int lo[3] = {a.xb[tx] - 1, y0, a.zb[ch] - 1};
-    const int hi[3] = {a.xb[tx] + TXn, y0 + R, a.zb[ch + 1] + 1};
-    int m = 0;
-    for (int d = 0; d < 3; d++) {
-      if (F->h_flag[d].empty()) continue;
-      for (int j = std::max(lo[d], 0); j <= std::min(hi[d], g.N[d] - 1) && !(m >> d & 1); j++)
-        for (int sft = 0; sft < 2; sft++) {
-          const size_t q = 2 * (size_t)(j + g.off[d]) + sft;
-          if (q >= F->h_flag[d].size()) continue;
-          const double kap = F->h_kap[d][q], sig = F->h_sig[d][q];
-          if (F->h_flag[d][q] || kap - sig != 1.0 || kap + sig != 1.0 || F->h_siginv[d][q] != 1.0)
-            m |= 1 << d;
-        }
-    }
-    return m;
-  };
-  for (int &v : F->gitems) {
-    const int m = pml_dirs(v, false);
-    v |= ((m & ~2) == 0 ? 2 : (m & ~4) == 0 ? 4 : 7) << 24;
-  }
-  for (int &v : narrow) v |= (((pml_dirs(v, true) & ~1) == 0 ? 1 : 7) << 24) | (int)0x80000000u;
-  // bits 27 / 28: the item's x-1 halo column (own rows) / y-1 halo row (own columns) lies
-  // in the box the lean kernel stores (lean chunk, lean columns and rows).  When the general
-  // launch follows the lean one (FusedArgs::lean_after) those lanes read B_new (== H_new:
-  // no PML there) instead of recomputing it from the old fields: identical values, fewer
-  // halo lines (profiles/README.md, round 2)
-  if (anylean) {
-    const int lsx0 = a.xb[a.lx0], lsx1 = a.xb[a.lx1 + 1] - 1;
-    const int lsy0 = a.yb[0], lsy1 = a.yb[a.ny] - 1;
-    auto mark = [&](int &v, bool nar) {
-      const int tx = v & 255, ty = (v >> 8) & 255, ch = (v >> 16) & 255;
-      if (!lean_ch(ch)) return;
-      const int *ybv = nar ? a.nyb : a.gyb;
-      const int x0 = a.xb[tx], x1 = a.xb[tx + 1] - 1, y0 = ybv[ty] - 1, y1 = ybv[ty + 1] - 1;
-      if (x0 - 1 >= lsx0 && x0 - 1 <= lsx1 && y0 + 1 >= lsy0 && y1 <= lsy1) v |= 1 << 27;
-      if (y0 >= lsy0 && y0 <= lsy1 && x0 >= lsx0 && x1 <= lsx1) v |= 1 << 28;
-    };
-    for (int &v : F->gitems) mark(v, false);
-    for (int &v : narrow) mark(v, true);
-  }
-  // one launch takes both shapes (bit 31 marks a 16-column tile): chunk-0 items
-  // first (the early launch of multi-rank steps), then the rest longest first
-  // (most planes), so the shortest items fill the launch's tail
-  std::vector<int> all;
-  all.reserve(F->gitems.size() + narrow.size());
-  for (int v : F->gitems)
-    if (((v >> 16) & 255) == 0) all.push_back(v);
-  for (int v : narrow)
-    if (((v >> 16) & 255) == 0) all.push_back(v);
-  a.ngen_e = (int)all.size();
-  std::vector<int> rest;
-  for (int v : F->gitems)
-    if (((v >> 16) & 255) != 0) rest.push_back(v);
-  for (int v : narrow)
-    if (((v >> 16) & 255) != 0) rest.push_back(v);
-  auto planes = [&](int v) {
-    const int ch = (v >> 16) & 255;
-    return a.zb[ch + 1] - a.zb[ch];
-  };
-  std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return planes(x) > planes(y); });
-  all.insert(all.end(), rest.begin(), rest.end());
-  F->gitems.swap(all);
-  a.ngen = (int)F->gitems.size();
-  a.ngen_n = a.ngen_ne = 0;
-  for (int k = 0; k < 3; k++) {
-    a.N[k] = g.N[k];
-    a.off[k] = g.off[k];
-    a.osh_lo[k] = g.owned_lo_sh[k];
-    a.osh_hi[k] = std::min(g.owned_hi_sh[k], G.hi[k]);
-    a.oun_lo[k] = g.owned_lo_un[k];
-    a.oun_hi[k] = std::min(g.owned_hi_un[k], G.hi[k]);
-  }
   // ---- shell: the top plane of a rank with an upper neighbour
   BoxList &bl = F->fused_shell;
   memset(&bl, 0, sizeof(bl));
@@ -2168,7 +1910,6 @@ FusedArgs &fused_args(mnl_fields *F) {
   FusedArgs &fa = F->fgeo;
   const DevFields &f = F->f;
   fa.blocks_per_cu = F->fused_bpc;
-  fa.dist = F->fused_dist;
   fa.nelem = (long long)F->nlocal;
   fa.C = F->S.courant;
   fa.st1 = F->g.st[1];
@@ -2203,7 +1944,6 @@ FusedArgs &fused_args(mnl_fields *F) {
   fa.tflag = nullptr;
   fa.uidx = F->d_uidx;
   fa.utab = F->d_utab;
-  fa.uflag = nullptr;
   fa.gflag = nullptr;
   if (F->d_uidx && F->uniform) {
     // flags of the current tile / chunk geometry (rebuilt if make_fused_boxes changed it)
@@ -2213,14 +1953,10 @@ FusedArgs &fused_args(mnl_fields *F) {
     for (int i = 0; i <= fa.ny; i++) mix(fa.yb[i]);
     for (int i = 0; i <= fa.nch; i++) mix(fa.zb[i]);
     for (int k = 0; k < 3; k++) mix(fa.L.lo[k]), mix(fa.L.hi[k]);
-    mix(fa.lx0), mix(fa.lx1), mix(fa.ly0), mix(fa.ly1), mix(fa.nch);
     for (int i = 0; i <= fa.ngy; i++) mix(fa.gyb[i]);
-    for (int i = 0; i <= fa.nny; i++) mix(fa.nyb[i]);
     for (int v : F->gitems) mix(v);
     for (int v : F->titems) mix(v);
-    const long long ntile = (long long)(fa.lx1 - fa.lx0 + 1) * (fa.ly1 - fa.ly0 + 1);
-    const size_t n = ntile > 0 ? (size_t)ntile * fa.nch : 0, ng = F->gitems.size();
-    const size_t nt = F->titems.size();
+    const size_t ng = F->gitems.size(), nt = F->titems.size();
     auto grow = [](unsigned *&p, size_t &cap, size_t want) {
       if (cap >= want) return true;
       if (p) hipFree(p);
@@ -2231,37 +1967,22 @@ FusedArgs &fused_args(mnl_fields *F) {
     };
     bool ok = true;
     if (F->uflag_sig != sig) {
-      ok = grow(F->d_uflag, F->uflag_n, n) && grow(F->d_gflag, F->gflag_n, ng) &&
-           grow(F->d_tflag, F->tflag_n, nt) &&
-           k_lean_uniform(fa, F->d_uflag, F->stream) == 0 &&
+      ok = grow(F->d_gflag, F->gflag_n, ng) && grow(F->d_tflag, F->tflag_n, nt) &&
            k_general_uniform(fa, F->d_gflag, F->stream) == 0 &&
            k_tile_uniform(fa, F->d_tflag, F->stream) == 0;
       F->uflag_sig = ok ? sig : 0;
       if (ok) {  // per-item cell counts of the mixed items (traffic model)
-        std::vector<unsigned> hl(n), hg(ng), ht(nt);
-        ok = (n == 0 || hipMemcpyAsync(hl.data(), F->d_uflag, n * 4, hipMemcpyDeviceToHost,
-                                       F->stream) == hipSuccess) &&
-             (nt == 0 || hipMemcpyAsync(ht.data(), F->d_tflag, nt * 4, hipMemcpyDeviceToHost,
+        std::vector<unsigned> hg(ng), ht(nt);
+        ok = (nt == 0 || hipMemcpyAsync(ht.data(), F->d_tflag, nt * 4, hipMemcpyDeviceToHost,
                                         F->stream) == hipSuccess) &&
              (ng == 0 || hipMemcpyAsync(hg.data(), F->d_gflag, ng * 4, hipMemcpyDeviceToHost,
                                         F->stream) == hipSuccess) &&
              hipStreamSynchronize(F->stream) == hipSuccess;
-        double ln = 0, gn = 0;
-        const int nlx = fa.lx1 - fa.lx0 + 1;
-        for (size_t i = 0; ok && i < n; i++) {
-          const int t = (int)(i / fa.nch), ch = (int)(i % fa.nch);
-          bool lean = false;
-          for (int r = 0; r < fa.nlzr; r++) lean = lean || (ch >= fa.lzr[r][0] && ch <= fa.lzr[r][1]);
-          if (!lean || hl[i] != ~0u) continue;
-          const int tx = fa.lx0 + t % nlx, ty = fa.ly0 + t / nlx;
-          ln += double(fa.xb[tx + 1] - fa.xb[tx]) * (fa.yb[ty + 1] - fa.yb[ty]) *
-                (fa.zb[ch + 1] - fa.zb[ch]);
-        }
+        double gn = 0;
         for (size_t i = 0; ok && i < ng; i++) {
           if (hg[i] != ~0u) continue;
           const int v = F->gitems[i], tx = v & 255, ty = (v >> 8) & 255, ch = (v >> 16) & 255;
-          const int *yb = (v & (int)0x80000000u) ? fa.nyb : fa.gyb;
-          gn += double(fa.xb[tx + 1] - fa.xb[tx]) * (yb[ty + 1] - yb[ty]) *
+          gn += double(fa.xb[tx + 1] - fa.xb[tx]) * (fa.gyb[ty + 1] - fa.gyb[ty]) *
                 (fa.zb[ch + 1] - fa.zb[ch]);
         }
         double tn = 0;
@@ -2271,23 +1992,19 @@ FusedArgs &fused_args(mnl_fields *F) {
           tn += double(fa.xb[tx + 1] - fa.xb[tx]) * (fa.yb[ty + 1] - fa.yb[ty]) *
                 (fa.zb[ch + 1] - fa.zb[ch]);
         }
-        F->lean_cells_nu = ln;
         F->gen_cells_nu = gn;
         F->tile_cells_nu = tn;
         if (!ok) F->uflag_sig = 0;
       }
     }
     if (ok) {
-      fa.uflag = n ? F->d_uflag : nullptr;
       fa.gflag = ng ? F->d_gflag : nullptr;
       fa.tflag = nt ? F->d_tflag : nullptr;
     }
   }
-  F->uflag_active = fa.uflag || fa.gflag || fa.tflag;
+  F->uflag_active = fa.gflag || fa.tflag;
   fa.ctr = F->d_fused_ctr;
   fa.clk = ItemClock{F->d_clk, F->d_clk_n, F->d_clk ? CLK_CAP : 0u, 0};
-  fa.ngrp = F->lean_groups;  // lean queue groups; general: gen_groups
-  fa.ngrp_gen = F->gen_groups;
   return fa;
 }
 
@@ -2296,12 +2013,7 @@ int fused_fail(const char *what, int kr) {
               hipGetErrorString(hipGetLastError()) + ")");
 }
 
-// CUs given to the general kernel when it runs beside the lean one: its share
-// of the step's work (general tile-planes cost ~2.5x a lean cell's bandwidth
-// time per cell), or MNL_GEN_CUS; 0 = run the two kernels one after the other
-int gen_split(const mnl_fields *F) { return F->gen_cus >= 0 ? F->gen_cus : 0; }
-
-// tile mode, one rank: CUs of the polarization chunks' general kernel beside the tile
+// one rank: CUs of the polarization chunks' general kernel beside the tile
 // kernel (0: after it on the same stream; the tuner's choice, or MNL_TILE_GEN_CUS)
 int tile_gen_split(const mnl_fields *F) {
   const int v = F->tile_gen_cus;
@@ -2337,7 +2049,7 @@ int step_fused_multi(mnl_fields *F, const SrcDev &sD, EB &ev_begin, EE &ev_end) 
   HIPCHK(hipEventRecord(F->ev_start, F->stream));
   HIPCHK(hipStreamWaitEvent(F->s_aux, F->ev_start, 0));
   HIPCHK(hipStreamWaitEvent(F->s_aux, F->ev_x0, 0));
-  int kr = F->tile_mode ? k_fused(fa, 5, F->s_aux, F->ctr_base) : 0;
+  int kr = k_fused(fa, 5, F->s_aux, F->ctr_base);
   if (!kr) kr = k_fused(fa, 2, F->s_aux, F->ctr_base);
   if (kr) return fused_fail("fused early kernel launch failed", kr);
   HIPCHK(hipEventRecord(F->ev_early, F->s_aux));
@@ -2347,16 +2059,14 @@ int step_fused_multi(mnl_fields *F, const SrcDev &sD, EB &ev_begin, EE &ev_end) 
   int k = ev_begin(TM_BINT);
   // the persistent main launch leaves TB_RES_CUS CUs to the chunk-0 launch on s_aux and
   // the slab-face work after it, so they cannot queue behind it for the whole step
-  fa.wg_limit = F->tile_mode ? k_cu_count() - TB_RES_CUS : 0;
-  kr = k_fused(fa, F->tile_mode ? 6 : 0, F->stream, F->ctr_base);
+  fa.wg_limit = k_cu_count() - TB_RES_CUS;
+  kr = k_fused(fa, 6, F->stream, F->ctr_base);
   fa.wg_limit = 0;
   if (kr) return fused_fail("fused kernel launch failed", kr);
   ev_end(k);
-  if (!F->tile_mode || fa.ngen > fa.ngen_e) {
+  if (fa.ngen > fa.ngen_e) {
     k = ev_begin(TM_GEN);
-    fa.lean_after = F->tile_mode ? 0 : lean_halo_reads(F);  // same stream, after the lean launch
     kr = k_fused(fa, 3, F->stream, F->ctr_base);
-    fa.lean_after = 0;
     if (kr) return fused_fail("fused general kernel launch failed", kr);
     ev_end(k);
   }
@@ -2757,8 +2467,8 @@ int tb_plan(mnl_fields *F) {
     if (L2.hi[0] - h.hi[0] < 8) h.hi[0] = L2.hi[0];
     holes.push_back(h);
   }
-  // polarization chunks (tile mode: the planes [pzl - 1, pzh + 2) over the whole x-y extent of
-  // G, make_tile_boxes): stepped by the general kernel, not by rim items; no two-step point
+  // polarization chunks (the planes [pzl - 1, pzh + 2) over the whole x-y extent of
+  // G, make_fused_boxes): stepped by the general kernel, not by rim items; no two-step point
   // within distance 2 of them (their E is stored, not chi1inv D)
   Box P;
   bool have_p = false;
@@ -2802,7 +2512,7 @@ int tb_plan(mnl_fields *F) {
   }
   if (two.empty() && F->nranks == 1) return 0;
   // ---- rim items: tile-kernel shapes (columns <= 64 from 128-byte boundaries, rows <= 14,
-  // chunks <= zc cut at the lean box's z range), bodies as make_tile_boxes
+  // chunks <= zc cut at the lean box's z range), bodies as make_fused_boxes
   // planes per rim item: its own setting (tuned with pairs), else the one-step chunk length
   const int zc = F->rim_zchunk > 0 ? std::min(F->rim_zchunk, FUSED_MAXCH)
                  : F->fused_zchunk > 0 ? std::min(F->fused_zchunk, FUSED_MAXCH) : 24;
@@ -3222,18 +2932,18 @@ int tb_mid_alloc(mnl_fields *F) {
 int tb_usable(mnl_fields *F, bool *ok) {
   *ok = false;
   // (no chi(2) NR box or upstream nonlinearity: the pairs have no E phase of their own.
-  // Polarization chunks (tile mode: the general items are exactly those chunks) step one step
+  // Polarization chunks (the general items are exactly those chunks) step one step
   // at a time in the general kernel beside each rim launch, on one rank (round 6, DESIGN.md
   // section 27); L2 keeps a distance of 2 from them)
   const bool pol_ok = F->f.npol > 0 && F->fgeo.ngen > 0 && F->nranks == 1 && F->tb_pol_on;
-  bool local = F->tb_enabled && F->fused && F->tile_mode &&
+  bool local = F->tb_enabled && F->fused &&
                ((F->fgeo.ngen == 0 && F->f.npol == 0) || pol_ok) && !F->nr && !F->upnl &&
                F->S.dim == 3 && F->slab_dir == 2;
   if (local && tb_plan(F)) return -1;
   if (local && F->tb_have && tb_mid_alloc(F)) local = false;
   if (F->tb_stats && !(local && F->tb_have))
-    fprintf(stderr, "tb: no pairs (enabled %d fused %d tile %d ngen %d dim %d slab %d dfts %zu have %d)\n",
-            (int)F->tb_enabled, (int)F->fused, (int)F->tile_mode, F->fgeo.ngen, F->S.dim,
+    fprintf(stderr, "tb: no pairs (enabled %d fused %d ngen %d dim %d slab %d dfts %zu have %d)\n",
+            (int)F->tb_enabled, (int)F->fused, F->fgeo.ngen, F->S.dim,
             F->slab_dir, F->dfts.size(), (int)F->tb_have);
   local = local && F->tb_have;
   if (F->nranks > 1) {  // every rank or none (their exchange sequences differ by mode)
@@ -3295,7 +3005,6 @@ FusedArgs gen_args(const FusedArgs &fa, const Set5 &o, const Set5 &n) {
     r.Bn[d] = n.B[d], r.Dn[d] = n.D[d], r.En[d] = n.E[d], r.Hn[d] = n.H[d], r.UBn[d] = n.UB[d];
   }
   r.wg_limit = 0;
-  r.lean_after = 0;
   return r;
 }
 
@@ -3803,30 +3512,9 @@ int step_batch(mnl_fields *F, int nsteps) {
       bool nr_done = false;  // the NR box's E phase already launched (beside the tile kernel)
       if (F->fused) {
         FusedArgs &fa = fused_args(F);
-        const int split = F->tile_mode ? 0 : gen_split(F);
         int kr;
-        if (split > 0) {
-          // general tiles on `split` CUs of a side stream, lean tiles on the others,
-          // concurrently (disjoint points, old buffers read-only)
-          if (!F->s_aux) {
-            HIPCHK(hipStreamCreateWithFlags(&F->s_aux, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&F->ev_start, hipEventDisableTiming | hipEventReleaseToDevice));
-            HIPCHK(hipEventCreateWithFlags(&F->ev_early, hipEventDisableTiming | hipEventReleaseToDevice));
-          }
-          HIPCHK(hipEventRecord(F->ev_start, F->stream));
-          HIPCHK(hipStreamWaitEvent(F->s_aux, F->ev_start, 0));
-          fa.wg_limit = split;
-          kr = k_fused(fa, 1, F->s_aux, F->ctr_base);
-          if (kr) return fused_fail("fused general kernel launch failed", kr);
-          HIPCHK(hipEventRecord(F->ev_early, F->s_aux));
-          fa.wg_limit = k_cu_count() - split;
-          kr = k_fused(fa, 0, F->stream, F->ctr_base);
-          fa.wg_limit = 0;
-          if (kr) return fused_fail("fused kernel launch failed", kr);
-          HIPCHK(hipStreamWaitEvent(F->stream, F->ev_early, 0));
-          F->fused_concurrent = true;
-        } else if (const int ts = F->tile_mode && fa.ngen > 0 ? tile_gen_split(F) : 0) {
-          // tile mode: the polarization chunks' general items on `ts` CUs of a side
+        if (const int ts = fa.ngen > 0 ? tile_gen_split(F) : 0) {
+          // the polarization chunks' general items on `ts` CUs of a side
           // stream beside the tile kernel on the others (both read only the old buffers
           // and write the ping-pong partners: no ordering between them)
           if (!F->s_aux) {
@@ -3854,16 +3542,12 @@ int step_batch(mnl_fields *F, int nsteps) {
           F->fused_concurrent = true;
         } else {
           F->fused_concurrent = false;
-          kr = k_fused(fa, F->tile_mode ? 4 : 0, F->stream, F->ctr_base);
+          kr = k_fused(fa, 4, F->stream, F->ctr_base);
           if (kr) return fused_fail("fused kernel launch failed", kr);
-          if (!F->tile_mode || fa.ngen > 0) {
+          if (fa.ngen > 0) {
             ev_end(k);
             k = ev_next(k, TM_GEN);
-            // lean mode: same stream, after the lean launch (tile mode: the general
-            // items are polarization chunks, whose halos no lean launch stores)
-            fa.lean_after = F->tile_mode ? 0 : lean_halo_reads(F);
             kr = k_fused(fa, 1, F->stream, F->ctr_base);
-            fa.lean_after = 0;
             if (kr) return fused_fail("fused general kernel launch failed", kr);
           }
         }
@@ -4270,7 +3954,6 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
     F->fused_zchunk_env = true;  // the tuner keeps it
   }
   if (const char *bp = getenv("MNL_FUSED_BPC")) F->fused_bpc = std::max(1, atoi(bp));
-  if (const char *tm = getenv("MNL_TILE")) F->tile_mode = atoi(tm) != 0;
   if (const char *tb = getenv("MNL_TB")) F->tb_enabled = atoi(tb) != 0, F->tb_env = true;
   if (const char *tz = getenv("MNL_TB_ZCHUNK"))
     F->tb_zchunk = std::max(0, atoi(tz)), F->tb_zchunk_env = true;
@@ -4286,10 +3969,8 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
   if (const char *tr = getenv("MNL_TB_RES")) F->tb_res = std::max(0, atoi(tr));
   if (const char *tp = getenv("MNL_TB_NOPAIR")) F->tb_nopair = atoi(tp) != 0;
   if (const char *bm = getenv("MNL_TILE_BODY_MASK")) F->tile_body_mask = atoi(bm);
-  if (const char *fd = getenv("MNL_FUSED_DIST")) F->fused_dist = atoi(fd) == 2 ? 2 : 1;
   if (const char *nf = getenv("MNL_NO_FUSED")) F->allow_fused = atoi(nf) == 0;
   if (const char *ne = getenv("MNL_NAN_EVERY")) F->nan_every = std::max(1, atoi(ne));
-  if (const char *gc = getenv("MNL_GEN_CUS")) F->gen_cus = std::max(0, atoi(gc));
   if (const char *sg = getenv("MNL_STAGGER")) F->stagger = std::max(0, atoi(sg)) / 128 * 128;
   if (const char *ar = getenv("MNL_ARENA")) F->arena_req = std::max(0, atoi(ar));
   if (const char *cg = getenv("MNL_CONTIG")) F->contig = atoi(cg) != 0;
@@ -4300,11 +3981,8 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
   };
   F->ownc = !env_is("MNL_NO_OWNC", '1');
   F->tile_zcut = !env_is("MNL_ZCUT", '0');
-  F->lean_halo = !env_is("MNL_LEAN_HALO", '0');
   F->no_palette = env_is("MNL_NO_PALETTE", '1');
   F->uniform = !env_is("MNL_UNIFORM", '0');
-  F->lean_groups = env_is("MNL_LEAN_GROUPS", '8') ? 8 : 1;
-  F->gen_groups = env_is("MNL_GEN_GROUPS", '8') ? 8 : 1;
   if (const char *e = getenv("MNL_TILE_GEN_CUS")) {
     F->tile_gen_cus = std::max(0, atoi(e));
     F->tile_gen_cus_env = true;
@@ -4921,7 +4599,7 @@ int mnl_fields_tune(mnl_fields *F, int reps, int *zchunk, int *gen_cus) {
   // the first step runs unfused (lazy first updates); the second takes the fused decision
   for (int i = 0; i < 2 && !F->fused; i++)
     if (fields_step(F, 1)) return -1;
-  if (!F->fused || !F->tile_mode) return 0;
+  if (!F->fused) return 0;
   const bool prof = F->profiling;  // restored with the timers after tuning
   double tms[16];
   long long tcnt[16];
@@ -4976,7 +4654,7 @@ int mnl_fields_tune(mnl_fields *F, int reps, int *zchunk, int *gen_cus) {
     F->tile_gen_cus = 0;
     double tm = 0, gm = 0;
     if (timed(&tm, &gm)) rc = -1;
-    if (!rc && F->fused && F->tile_mode && gm > 0) {
+    if (!rc && F->fused && gm > 0) {
       // start from the split that gives both launches the same time at their measured
       // one-after-the-other rates, in multiples of 8 CUs (one per XCD)
       const int cus = k_cu_count();
@@ -5278,25 +4956,21 @@ int mnl_fields_set_profiling(mnl_fields *F, int on) {
 // every point reads B, D and writes B, D (96 B) + chi1inv (4 B palette word
 // or 3 doubles); PML state is counted per (point, component) where the
 // reference keeps it: f_u of B / D, separate H, W-form E (read + write 16 B).
-// lean: the same for the lean tiles only (no PML state there).
+// lean_bytes: the tile kernel's share, gen_bytes: the general kernel's (polarization chunks).
 void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
   const DevGrid &g = F->g;
   const FusedArgs &a = F->fgeo;
   int nu = 0;
   for (int d = 0; d < 3; d++) nu += F->f.inveps[d] ? 1 : 0;
   const double ub = F->d_uidx ? 4.0 : 8.0 * nu;
-  // with per-item uniform palette words only the mixed items read chi1inv per cell
-  const bool uni = F->d_uidx && F->uflag_active && F->lean_cells_nu >= 0;
-  const double lean_u = uni ? F->lean_cells_nu : double(F->lean_cells);
-  *lean_bytes = double(F->lean_cells) * 96.0 + lean_u * ub;
   double extra = 0, extra_t = 0;
   // count of local indices j in [lo, hi] of axis e with an optional flag condition;
-  // zsel (axis 2): 0 every plane, 1 the tile kernel's planes, 2 the others
-  int zsel = 0;
+  // zsel (axis 2): 1 the tile kernel's planes, 2 the others
+  int zsel = 1;
   auto cnt = [&](int e, int lo, int hi, int qshift, bool need_flag) -> double {
     double n = 0;
     for (int j = lo; j <= hi; j++) {
-      if (e == 2 && zsel && (j < 0 || j >= (int)F->tile_z.size() ||
+      if (e == 2 && (j < 0 || j >= (int)F->tile_z.size() ||
                              (F->tile_z[j] != 0) != (zsel == 1)))
         continue;
       if (need_flag) {
@@ -5307,8 +4981,7 @@ void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
     }
     return n;
   };
-  for (int pass = 0; pass < (F->tile_mode ? 2 : 1); pass++) {
-    zsel = F->tile_mode ? (pass == 0 ? 1 : 2) : 0;
+  for (zsel = 1; zsel <= 2; zsel++) {
     for (int c = 0; c < 3; c++)
       for (int kind = 0; kind < 4; kind++) {
         // kind 0: f_u of B_c (flag along c+2, shifted); 1: H_c (along c, unshifted);
@@ -5325,11 +4998,10 @@ void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
         (zsel == 1 ? extra_t : extra) += 16.0 * n;
       }
   }
-  if (F->tile_mode) {  // tile kernel = "lean" slot of the statistics, general = the rest
-    const bool tuni = F->d_uidx && F->uflag_active && F->tile_cells_nu >= 0;
-    *lean_bytes = double(F->tile_cells) * 96.0 +
-                  (tuni ? F->tile_cells_nu : double(F->tile_cells)) * ub + extra_t;
-  }
+  // with per-item uniform palette words only the mixed items read chi1inv per cell
+  const bool tuni = F->d_uidx && F->uflag_active && F->tile_cells_nu >= 0;
+  *lean_bytes = double(F->tile_cells) * 96.0 +
+                (tuni ? F->tile_cells_nu : double(F->tile_cells)) * ub + extra_t;
   // polarization boxes: stored E (read + write), P and Pprev (read + write) and
   // sigma (read) per component and susceptibility
   for (int k = 0; k < F->f.npol; k++) {
@@ -5343,16 +5015,9 @@ void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
     for (int d = 0; d < 3; d++) nc += F->f.pol[k].P[d] ? 1 : 0;
     extra += n * nc * (40.0 + (k == 0 ? 16.0 : 0.0));
   }
-  double gcells = 1;
-  for (int e = 0; e < 3; e++) gcells *= double(F->fusedG.hi[e] - F->fusedG.lo[e] + 1);
-  if (F->tile_mode) {
-    const bool guni = F->d_uidx && F->uflag_active && F->gen_cells_nu >= 0;
-    *gen_bytes = double(F->gen_cells) * 96.0 +
-                 (guni ? F->gen_cells_nu : double(F->gen_cells)) * ub + extra;
-    return;
-  }
-  const double gen_u = uni ? F->gen_cells_nu : gcells - double(F->lean_cells);
-  *gen_bytes = (gcells - double(F->lean_cells)) * 96.0 + gen_u * ub + extra;
+  const bool guni = F->d_uidx && F->uflag_active && F->gen_cells_nu >= 0;
+  *gen_bytes = double(F->gen_cells) * 96.0 +
+               (guni ? F->gen_cells_nu : double(F->gen_cells)) * ub + extra;
 }
 
 int mnl_fields_kernel_stats(mnl_fields *F, int which, long long *launches, double *total_ms,
@@ -5516,7 +5181,7 @@ int mnl_fields_tb_info(mnl_fields *F, double *out, int n) {
 int mnl_fields_mode(mnl_fields *F, int *fused) {
   if (!F) return fail("null fields");
   *fused = (F->fused ? 1 : 0) | (F->fused && F->d_uidx ? 2 : 0) | (F->contig ? 4 : 0) |
-           (F->fused && F->tile_mode ? 16 : 0) | (F->fused && F->fused_concurrent ? 32 : 0) |
+           (F->fused ? 16 : 0) | (F->fused && F->fused_concurrent ? 32 : 0) |
            (std::min(F->contig_fallbacks, 255) << 8);
   return 0;
 }

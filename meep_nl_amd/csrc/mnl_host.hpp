@@ -281,17 +281,14 @@ struct mnl_fields {
   std::vector<int> gitems;   // general-kernel items
   int *d_gitems = nullptr;
   size_t d_gitems_cap = 0;
-  // tile mode (MNL_TILE, default on): one tile kernel over every chunk outside the
-  // polarization chunks (lean + PML bodies), the general kernel over those chunks only
-  bool tile_mode = true;
+  // one tile kernel over every chunk outside the polarization chunks (lean + PML bodies),
+  // the general kernel over those chunks only
   bool tile_zcut = true;      // cut z chunks at the lean box's z range (short z-PML items)
   int tile_body_mask = -1;   // MNL_TILE_BODY_MASK: step only these bodies (timing experiments)
   // diagnostic / A-B switches, read once when the fields are created (mnl_fields_create)
   bool ownc = true;           // MNL_NO_OWNC=1: no OWNC item flag
-  bool lean_halo = true;      // MNL_LEAN_HALO=0: general tiles recompute the lean halo
   bool no_palette = false;    // MNL_NO_PALETTE=1: per-cell chi1inv loads, no byte palette
   bool uniform = true;        // MNL_UNIFORM=0: per-cell palette loads in uniform items too
-  int lean_groups = 1, gen_groups = 1;  // MNL_LEAN_GROUPS / MNL_GEN_GROUPS: 1 or 8 queues
   bool tile_gen_cus_env = false;        // MNL_TILE_GEN_CUS given (the tuner keeps it)
   bool fused_zchunk_env = false;        // MNL_FUSED_ZCHUNK given (the tuner keeps it)
   bool tb_env = false, tb_zchunk_env = false;  // MNL_TB / MNL_TB_ZCHUNK given (the same)
@@ -310,7 +307,7 @@ struct mnl_fields {
   long long tile_cells = 0;     // own cells of the tile items
   double tile_cells_nu = -1;    // ... of those that read a palette index per cell
   std::vector<char> tile_z;     // per local z plane: stepped by the tile kernel
-  long long lean_cells = 0, gen_cells = 0;
+  long long gen_cells = 0;      // own cells of the general items
   FusedTab d_tab{};          // per-direction PML coefficient tables for the fused kernels
   // multi-rank fused stepping: chunk 0 on s_aux, halo exchange on s_comm,
   // overlapped with the interior kernels on `stream` (DESIGN.md "Multi-GPU")
@@ -322,10 +319,8 @@ struct mnl_fields {
   double *pp_UB[3] = {nullptr, nullptr, nullptr};
   int fused_zchunk = 0;
   int fused_bpc = 1;
-  int fused_dist = 1;
-  int gen_cus = -1;  // CUs for the general kernel running beside the lean one (0: serial)
-  bool fused_concurrent = false;  // last fused step ran lean + general concurrently
-  int tile_gen_cus = 0;           // tile mode: general kernel beside the tile kernel (CUs)
+  bool fused_concurrent = false;  // last fused step ran the tile + general kernels concurrently
+  int tile_gen_cus = 0;           // general kernel beside the tile kernel (CUs; 0: after it)
   unsigned long long *d_fused_ctr = nullptr;  // work-item counters of the fused kernels
   unsigned long long ctr_base[FUSED_NCTR] = {0};  // their values at the next launch
   int stagger = 0, nstagger = 0;  // dev_alloc offset step (bytes) for field arrays
@@ -340,14 +335,12 @@ struct mnl_fields {
   bool any_dsrc_w = false;  // a D current source on a W-form (PML-along-E) point
   unsigned *d_uidx = nullptr;  // chi1inv palette indices over fusedG (null: f64 chi1inv)
   double *d_utab = nullptr;    // 3 x 256 palette values
-  unsigned *d_uflag = nullptr;  // per lean item: uniform palette word or ~0u (k_lean_uniform)
-  size_t uflag_n = 0;
   unsigned long long uflag_sig = 0;  // geometry the flags were built for
   unsigned *d_gflag = nullptr;  // per general item (k_general_uniform)
   size_t gflag_n = 0;
-  // cells of lean / general items that still read a palette index per cell (the
-  // algorithmic bytes of bench.py's roofline count 4 B of chi1inv for those only)
-  double lean_cells_nu = -1, gen_cells_nu = -1;
+  // cells of general items that still read a palette index per cell (the algorithmic
+  // bytes of bench.py's roofline count 4 B of chi1inv for those only)
+  double gen_cells_nu = -1;
   bool uflag_active = false;
   bool allow_fused = true;
   // the reference allocates H (as a copy of B) and the W auxiliary fields (as a
@@ -463,7 +456,6 @@ struct mnl_fields {
     if (d_gitems) hipFree(d_gitems);
     if (d_titems) hipFree(d_titems);
     if (d_tflag) hipFree(d_tflag);
-    if (d_uflag) hipFree(d_uflag);
     if (d_gflag) hipFree(d_gflag);
     for (void *p : {(void *)d_tb_ritems, (void *)d_tb_rgeo, (void *)d_tb_rflag, (void *)d_tb_uflag,
                     (void *)d_tb_items})

@@ -228,30 +228,27 @@ struct SrcLayers {
 int k_source(int ft, const DevGrid &g, const DevFields &f, const SrcDev &s, int step,
              void *stream);
 // Fused step (DESIGN.md "Fused step"): one pass per fields::step() over box G
-// (curl B -> H -> curl D -> E, 3-D, no dispersion/NR/B sources).  G is tiled
-// into 64 x 14 column tiles and z chunks whose bounds come from the host
-// (xb/yb/zb, inclusive starts, last entry = end + 1).  Tiles whose whole
-// footprint lies in the lean box L (no PML, every component owned) run the
-// lean body; every other tile runs the general body (per-point PML branch
+// (curl B -> H -> curl D -> E, 3-D, no NR/B sources).  G is tiled into 64 x 14
+// column tiles and z chunks whose bounds come from the host (xb/yb/zb, inclusive
+// starts, last entry = end + 1).  The tile kernel steps every chunk outside the
+// polarization chunks: tiles whose whole footprint lies in the lean box L (no PML,
+// every component owned) run the lean body, the others a PML body.  The polarization
+// chunks run the general body in 64 x FUSED_GW_ROWS tiles (gyb; per-point PML branch
 // selection, H/E W updates, per-component ownership).  Inside G, E of a point
 // is implicit (= chi1inv * D, never stored) unless the point is owned and in
 // a PML chunk along the E direction (then it is stored, ping-pong).
 constexpr int FUSED_MAXX = 64, FUSED_MAXY = 160, FUSED_MAXZ = 160;
 constexpr int FUSED_MAXCH = 64;  // longest general chunk (planes)
-constexpr int FUSED_MAXGY = 256, FUSED_MAXNY = 64;
+constexpr int FUSED_MAXGY = 256;
 // general items pack tx, ty, chunk in 8 bits each (mnl_kernels.hip, general_item)
 static_assert(FUSED_MAXZ <= 256 && FUSED_MAXX <= 256 && FUSED_MAXGY <= 256, "item encoding");
 #ifndef MNL_GW_ROWS
 #define MNL_GW_ROWS 10
 #endif
-#ifndef MNL_GN_ROWS
-#define MNL_GN_ROWS 39
-#endif
 #ifndef MNL_GEN_BPC
 #define MNL_GEN_BPC 1
 #endif
-constexpr int FUSED_GW_ROWS = MNL_GW_ROWS;  // general kernel, wide tiles: own rows per tile
-constexpr int FUSED_GN_ROWS = MNL_GN_ROWS;  // general kernel, 16-column tiles: own rows per tile
+constexpr int FUSED_GW_ROWS = MNL_GW_ROWS;  // general kernel: own rows per tile
 constexpr int FUSED_GEN_BPC = MNL_GEN_BPC;  // general kernel workgroups per CU
 #ifndef MNL_GEN_WPE
 #define MNL_GEN_WPE 1
@@ -281,19 +278,14 @@ struct FusedArgs {
   Box G;              // fused domain (stores only inside G)
   int nx, ny, nch;    // tiles along x, y; chunks along z
   int xb[FUSED_MAXX + 1], yb[FUSED_MAXY + 1], zb[FUSED_MAXZ + 1];
-  int ngy;            // general wide-tile rows (<= FUSED_GW_ROWS each)
+  int ngy;            // general tile rows (<= FUSED_GW_ROWS each)
   int gyb[FUSED_MAXGY + 1];
-  int nny;            // general 16-column-tile rows (<= FUSED_GN_ROWS each)
-  int nyb[FUSED_MAXNY + 1];
-  int lx0, lx1, ly0, ly1;      // lean x / y tile index ranges (inclusive)
-  int nlzr, lzr[4][2];         // lean chunk index ranges (inclusive), up to 4
   int N[3];           // local points per axis (array extents)
   int off[3];         // global index of local index 0 per axis
   int osh_lo[3], osh_hi[3], oun_lo[3], oun_hi[3];  // owned ranges within G per axis
   int blocks_per_cu;  // persistent workgroups per CU (default 1)
   int wg_limit;       // > 0: at most this many persistent workgroups (CU split between
-                      // the lean and general kernels running concurrently)
-  int dist;           // lean-body prefetch distance in planes (1 or 2)
+                      // the tile and general kernels running concurrently)
   long long nelem;    // elements per field array (selects 32-bit offsets)
   double C;
   long long st1, st2;
@@ -317,27 +309,20 @@ struct FusedArgs {
   PolDev pol[MAX_POL];
   Box pbox;                     // union of the pols' nonzero boxes (empty: lo > hi)
   Box xbox;                     // chi(2) box + 1 (inside pbox): E / P left to the NR kernel
-  const int *gitems;           // general items: tx | ty << 8 | ch << 16; wide, then narrow
-  int ngen, ngen_n;             // wide / narrow item counts (chunk-major order)
-  int ngen_e, ngen_ne;          // leading items of chunk 0 (the early launch of multi-rank steps)
+  const int *gitems;            // general items: tx | ty << 8 | ch << 16 | pml directions << 24
+  int ngen;                     // their count (chunk-major order)
+  int ngen_e;                   // leading items of chunk 0 (the early launch of multi-rank steps)
   int gbeg, gend, ctr_line;     // set per launch by k_fused: item range and counter line
   unsigned long long cbase;     // counter value at launch start (counters are never reset)
-  int ngrp;                     // work queues (1 or 8: one per XCD group, blockIdx % 8)
-  int ngrp_gen;                 // the same for the general kernels (k_fused copies it to ngrp)
-  const unsigned *gflag;        // general items (index in gitems): the same (k_general_uniform)
-  const unsigned *uflag;        // lean items (tile * nch + ch): the palette word shared by
+  const unsigned *gflag;        // general items (index in gitems): the palette word shared by
                                 // every cell whose chi1inv the item uses, or ~0u (mixed);
-                                // null: none (k_lean_uniform)
-  int lean_after;               // general launch follows the lean launch of this step on the
-                                // same stream: halo B_new of lean-stored points is read, not
-                                // recomputed (item bits 27 / 28)
+                                // null: none (k_general_uniform)
   // tile kernel: items tx | ty << 8 | ch << 16 | body << 24 over the
   // lean-shaped tiles (xb, yb, zb) of every chunk outside the polarization chunks; chunk-0
   // items first (ntit_e of them: the early launch of multi-rank steps)
   const int *titems;
   int ntit, ntit_e;
   const unsigned *tflag;        // per tile item: palette word uniform over its footprint, or ~0u
-  unsigned long long cbg[8];    // lean queue g: counter line g's value at launch start
   unsigned long long *ctr;      // FUSED_NCTR work-queue counters (128 B apart); see cbase
   // explicit own boxes of the tile items (null: tx / ty / ch index xb / yb / zb): per item
   // x0 | x1 << 16 (columns, x0 128-byte aligned), yfirst | y1 << 16 (own rows), zs | ze << 16,
@@ -433,20 +418,19 @@ int k_tile_items(const FusedArgs &a, const int *items, const int *geo, const uns
 // per item of that list: the palette word uniform over its footprint, or ~0u
 int k_tile_items_uniform(const FusedArgs &a, const int *items, const int *geo, int n,
                          unsigned *flags, void *stream);
-// which: 0 = lean tiles, 1 = all general tiles, 2 = general tiles of chunk 0
-// only (early launch), 3 = the other general tiles; tile kernel: 4 = all tile items,
-// 5 = tile items of chunk 0 (early launch), 6 = the other tile items.  Every launch reads old /
-// writes new buffers only, on disjoint points, so any order is valid.
+// which: general kernel: 1 = all general items, 2 = the general items of chunk 0 (early
+// launch), 3 = the other general items; tile kernel: 4 = all tile items, 5 = tile items of
+// chunk 0 (early launch), 6 = the other tile items (anything else: 2, bad argument).  Every
+// launch reads old / writes new buffers only, on disjoint points, so any order is valid.
 // bases[FUSED_NCTR]: host copy of each counter line's value, advanced by every launch
 // (items + workgroups), so no counter reset (memset launch) is needed per step
-// counter lines: 0-7 lean queues, 8-11 general (wide/narrow x all/early, one
-// queue), FUSED_GLINE0 + (line - 8) * 8 + g: general line split per XCD group g
-constexpr int FUSED_GLINE0 = 16, FUSED_NCTR = 48;
+// counter lines (one work queue each): 0-2 tile kernel (all / early / rest), 3 two-step
+// kernel, 4-5 k_tile_items, 8 / 10 general kernel (all and rest / early)
+constexpr int FUSED_NCTR = 16;
 int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bases);
-// per lean item, whether the chi1inv palette word is uniform over the cells it uses
-// (flags: ntile * nch words); the lean kernel then reads one cached word instead of
-// a palette index per cell
-int k_lean_uniform(const FusedArgs &a, unsigned *flags, void *stream);
+// per tile / general item, the chi1inv palette word when it is uniform over the cells the
+// item uses, else ~0u (flags: one word per item); the kernels then read one cached word
+// instead of a palette index per cell
 int k_tile_uniform(const FusedArgs &a, unsigned *flags, void *stream);
 int k_general_uniform(const FusedArgs &a, unsigned *flags, void *stream);
 int k_cu_count();

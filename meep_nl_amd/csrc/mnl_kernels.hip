@@ -1672,7 +1672,6 @@ struct ItemGeo {
   int y0;      // halo row; own rows y0+1 .. y1
   int y1;
   int zs, ze;  // planes [zs, ze)
-  bool lmx, lmy;  // general body: x-1 halo column / y-1 halo row read B_new (lean-stored)
   unsigned uw;    // general body: palette word uniform over the item, or ~0u
 };
 
@@ -1820,14 +1819,7 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
   }
   const int oy = row;
   const int gx = x0 + ox, gy = y0 + oy;
-  // lean-halo lanes: the x-1 column (col 0) / the y-1 row (row 0) of a tile whose halo
-  // the lean kernel has already stored this step.  Nobody reads their E (LDS column 0 /
-  // row 0 of sE feed only their own recompute), and their new B equals the stored B_new
-  // (H == B outside PML), so they load the two components the neighbours read and
-  // nothing else.
-  const bool lmode = ownlike && ((col == 0 && it.lmx) || (w < NW && row == 0 && it.lmy));
-  const bool lmcol = col == 0;  // x-1 column: Hy, Hz read by col 1; y-1 row: Hx, Hz by row 1
-  // lanes past the tile's columns x1+1 / rows y1+1 (narrow or short tiles) load nothing
+  // lanes past the tile's columns x1+1 / rows y1+1 (short tiles) load nothing
   const bool inA = ownlike && gx >= 0 && gx < a.N[0] && gy >= 0 && gy < a.N[1] &&
                    gx <= it.x1 + 1 && gy <= it.y1 + 1;
   const unsigned cb = (unsigned)((gx + (long long)gy * a.st1) * 8);
@@ -1984,7 +1976,7 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
 
   // prologue: E_old(zs-1)
   double ex = 0, ey = 0, ez = 0;
-  if (!lmode) {
+  {
     const int z = zlo;
     const unsigned o = cbl + (unsigned)zc(z) * s2;
     const unsigned oz = ownz_of(z);
@@ -2017,21 +2009,8 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
   for (int k = zlo; k < ze; k++) {
     {
       const int kl = k;
-      GAux ax = {};
-      GBatch<UMODE> c = {};
-      double nb0 = 0, nb1 = 0, nb2 = 0;  // lean-halo lanes: B_new of plane k
-      if (!lmode) {
-        ax = load_aux(kl);
-        c = load(kl);
-      } else {
-        const unsigned ok = cbl + (unsigned)zc(kl) * s2;
-        if (lmcol) {
-          nb1 = ldg(sgpr_ptr(a.Bn[1]), ok);
-        } else {
-          nb0 = ldg(sgpr_ptr(a.Bn[0]), ok);
-        }
-        nb2 = ldg(sgpr_ptr(a.Bn[2]), ok);
-      }
+      const GAux ax = load_aux(kl);
+      const GBatch<UMODE> c = load(kl);
       const int pz = tpz(kl), pz1 = tpz(kl + 1);
       const unsigned oz = ownz_of(kl), oz1 = ownz_of(kl + 1);
       const bool wz1 = ((AX & 4) && sFz[pz1][1] != 0);
@@ -2093,7 +2072,6 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
       double Hx = fxu ? ax.ho0 + (tx_u.kps * Bx - tx_u.kms * c.b0) : Bx;
       double Hy = fyu ? ax.ho1 + (ty_u.kps * By - ty_u.kms * c.b1) : By;
       double Hz = fzu ? ax.ho2 + (tz_u.kps * Bz - tz_u.kms * c.b2) : Bz;
-      if (lmode) Hx = nb0, Hy = nb1, Hz = nb2;  // never stored by these lanes
       const bool kin = k >= zs && k < ze;
       const bool sk = stl && kin;
       {
@@ -2252,76 +2230,50 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
 }
 
 // General tiles: items from the host-built list a.gitems (tx | ty << 8 | ch << 16 |
-// pml directions << 24, bit 31 set for a 16-column tile).  One launch takes both tile shapes, so the
-// two share one tail:
-// TX = 64: tiles of <= 64 columns x FUSED_GW_ROWS rows (ty indexes a.gyb);
-// TX = 16: the narrow x-face tiles, 16 columns x FUSED_GN_ROWS rows (ty indexes
-// a.nyb), four rows per wave so a plane step does as much work as a wide tile.
-// 12 waves either way (168 VGPRs per lane).
-template <int TX>
-struct GenShape {
-  static constexpr int NW = TX == 64 ? FUSED_GW_ROWS + 1 : (FUSED_GN_ROWS + 1) / 4;
-  static constexpr int R = NW * (64 / TX);
-  static constexpr int WAVES = NW + (2 * R + 63) / 64;
-};
-static_assert(GenShape<64>::R - 1 == FUSED_GW_ROWS && GenShape<16>::R - 1 == FUSED_GN_ROWS,
-              "general tile rows");
-static_assert(GenShape<64>::WAVES == GenShape<16>::WAVES, "both tile shapes run in one workgroup");
-constexpr int GEN_WAVES = GenShape<64>::WAVES;
+// pml directions << 24): tiles of <= GEN_TX columns x FUSED_GW_ROWS rows (ty indexes a.gyb),
+// one row per wave plus the halo waves: 12 waves (168 VGPRs per lane).
+constexpr int GEN_TX = 64;
+constexpr int GEN_R = FUSED_GW_ROWS + 1;  // rows of a tile's footprint (row 0 = the y-1 halo row)
+constexpr int GEN_WAVES = GEN_R + (2 * GEN_R + 63) / 64;
 
-template <int TX>
-struct GenLds {  // LDS of one tile shape (the two shapes share it through a union)
-  static constexpr int R = GenShape<TX>::R;
-  double sE[3][R + 1][TX + 2];
-  double sB[3][R][TX + 1];
-  TabE sTx[TX + 2][2], sTy[R + 1][2], sTz[TPZ][2];
-  unsigned char sFx[TX + 2][2], sFy[R + 1][2], sFz[TPZ][2];
+struct GenLds {
+  double sE[3][GEN_R + 1][GEN_TX + 2];
+  double sB[3][GEN_R][GEN_TX + 1];
+  TabE sTx[GEN_TX + 2][2], sTy[GEN_R + 1][2], sTz[TPZ][2];
+  unsigned char sFx[GEN_TX + 2][2], sFy[GEN_R + 1][2], sFz[TPZ][2];
 };
 
-template <int UMODE, int TX, int POL, int AX>
-__device__ __forceinline__ void general_item(KFA &a, int item, unsigned uw,
-                                             GenLds<TX> &L, const double (*sU)[256]) {
+template <int UMODE, int POL, int AX>
+__device__ __forceinline__ void general_item(KFA &a, int item, unsigned uw, GenLds &L,
+                                             const double (*sU)[256]) {
   const int tx = item & 255, ty = (item >> 8) & 255, ch = (item >> 16) & 255;
-  const auto *yb = TX == 64 ? a.gyb : a.nyb;
   ItemGeo itg;
   itg.x0 = a.xb[tx];
   itg.x1 = a.xb[tx + 1] - 1;
-  itg.y0 = yb[ty] - 1;
-  itg.y1 = yb[ty + 1] - 1;
+  itg.y0 = a.gyb[ty] - 1;
+  itg.y1 = a.gyb[ty + 1] - 1;
   itg.zs = a.zb[ch];
   itg.ze = a.zb[ch + 1];
-  itg.lmx = a.lean_after && (item & (1 << 27));
-  itg.lmy = a.lean_after && (item & (1 << 28));
   itg.uw = uw;
-  fused_general<UMODE, TX, GenShape<TX>::R, GenShape<TX>::NW, POL, AX>(
-      a, itg, L.sE, L.sB, sU, L.sTx, L.sTy, L.sTz, L.sFx, L.sFy, L.sFz);
+  fused_general<UMODE, GEN_TX, GEN_R, GEN_R, POL, AX>(a, itg, L.sE, L.sB, sU, L.sTx, L.sTy, L.sTz,
+                                                      L.sFx, L.sFy, L.sFz);
 }
 
 template <int UMODE, int POL>
 __global__ __launch_bounds__(64 * GEN_WAVES, FUSED_GEN_WPE) void fused_general_kernel(FusedArgs a) {
   __shared__ double sU[UMODE == 2 ? 3 : 1][256];
-  __shared__ union {
-    GenLds<64> w;
-    GenLds<16> n;
-  } L;
+  __shared__ GenLds L;
   __shared__ int s_item;
   __shared__ unsigned s_uw;
   if (UMODE == 2)
     for (int i = threadIdx.x; i < 3 * 256; i += blockDim.x) sU[i >> 8][i & 255] = a.utab[i];
-  // ngrp > 1: the workgroups sharing an XCD (blockIdx % ngrp) take a contiguous
-  // share of the item list from their own counter line
-  const int grp = a.ngrp > 1 ? (int)(blockIdx.x % a.ngrp) : 0;
-  const int ntot = a.gend - a.gbeg;
-  const int base = a.gbeg + (int)((long long)ntot * grp / a.ngrp);
-  const int n = a.gbeg + (int)((long long)ntot * (grp + 1) / a.ngrp) - base;
-  unsigned long long *ctr =
-      a.ctr + 16 * (a.ngrp > 1 ? FUSED_GLINE0 + (a.ctr_line - 8) * 8 + grp : a.ctr_line);
-  const unsigned long long cb = a.ngrp > 1 ? a.cbg[grp] : a.cbase;
+  const int n = a.gend - a.gbeg;
+  unsigned long long *ctr = a.ctr + 16 * a.ctr_line;
   for (;;) {
     if (threadIdx.x == 0) {
-      const unsigned long long v = atomicAdd(ctr, 1ULL) - cb;
-      s_item = v < (unsigned long long)(n) ? a.gitems[base + v] : -1;
-      s_uw = (v < (unsigned long long)(n) && UMODE == 2 && a.gflag) ? a.gflag[base + v] : ~0u;
+      const unsigned long long v = atomicAdd(ctr, 1ULL) - a.cbase;
+      s_item = v < (unsigned long long)(n) ? a.gitems[a.gbeg + v] : -1;
+      s_uw = (v < (unsigned long long)(n) && UMODE == 2 && a.gflag) ? a.gflag[a.gbeg + v] : ~0u;
     }
     __syncthreads();  // also separates LDS use of consecutive items
     const int item = s_item;
@@ -2330,17 +2282,12 @@ __global__ __launch_bounds__(64 * GEN_WAVES, FUSED_GEN_WPE) void fused_general_k
     // bits 24-26: the PML directions of the tile's footprint (host); a body with
     // the other directions' tables fixed at identity runs fewer instructions
     const int ax = (item >> 24) & 7;
-    if (item & (int)0x80000000u) {
-      if (ax == 1)
-        general_item<UMODE, 16, POL, 1>(*kargs_opaque(), item, uw, L.n, sU);
-      else
-        general_item<UMODE, 16, POL, 7>(*kargs_opaque(), item, uw, L.n, sU);
-    } else if (ax == 2) {
-      general_item<UMODE, 64, POL, 2>(*kargs_opaque(), item, uw, L.w, sU);
+    if (ax == 2) {
+      general_item<UMODE, POL, 2>(*kargs_opaque(), item, uw, L, sU);
     } else if (ax == 4) {
-      general_item<UMODE, 64, POL, 4>(*kargs_opaque(), item, uw, L.w, sU);
+      general_item<UMODE, POL, 4>(*kargs_opaque(), item, uw, L, sU);
     } else {
-      general_item<UMODE, 64, POL, 7>(*kargs_opaque(), item, uw, L.w, sU);
+      general_item<UMODE, POL, 7>(*kargs_opaque(), item, uw, L, sU);
     }
   }
 }
@@ -3450,7 +3397,6 @@ __device__ __forceinline__ ItemGeo tile_item_geo(const FusedArgs &a, int item, i
     itg.zs = a.zb[ch];
     itg.ze = a.zb[ch + 1];
   }
-  itg.lmx = itg.lmy = false;
   itg.uw = ~0u;
   return itg;
 }
@@ -3549,115 +3495,39 @@ void launch_tile(const FusedArgs &t, int um, dim3 grd, hipStream_t s) {
   }
 }
 
-// Lean tiles only (the original two-launch fused step: this kernel, then
-// fused_general_kernel over the PML / boundary tiles; MNL_TILE=0).  Work queues,
-// chunk-major: consecutive items are neighbouring tiles of one chunk, so the
-// workgroups sweep z roughly together.  With ngrp = 8 the workgroups sharing an XCD
-// (blockIdx % 8, observed round-robin placement; speed only) own a contiguous range of
-// each chunk's tiles (x fastest), so the halo lines neighbouring tiles share are
-// fetched once into that XCD's L2.
-template <int UMODE, int DIST>
-__global__ __launch_bounds__(1024) void fused_kernel(FusedArgs a) {
-  __shared__ double sU[UMODE == 2 ? 3 : 1][256];
-  __shared__ double sE[3][FR + 1][FXL];
-  __shared__ double sB[3][FR][FXL];
-  __shared__ long long s_item;
-  if (UMODE == 2) {  // palette -> LDS (visible after the first barrier below)
-    for (int i = threadIdx.x; i < 3 * 256; i += 1024) sU[i >> 8][i & 255] = a.utab[i];
-  }
-  int nlch = 0;
-  for (int r = 0; r < a.nlzr; r++) nlch += a.lzr[r][1] - a.lzr[r][0] + 1;
-  const int nlx = a.lx1 - a.lx0 + 1;
-  const long long ntile = (long long)nlx * (a.ly1 - a.ly0 + 1);
-  const int grp = a.ngrp > 1 ? (int)(blockIdx.x % a.ngrp) : 0;
-  const long long gt0 = ntile * grp / a.ngrp, gt1 = ntile * (grp + 1) / a.ngrp;
-  const long long gtile = gt1 - gt0;
-  unsigned long long *gctr = a.ctr + 16 * grp;
-  const unsigned long long gbase = a.ngrp > 1 ? a.cbg[grp] : a.cbase;
-  for (;;) {
-    if (threadIdx.x == 0) {
-      const unsigned long long v = atomicAdd(gctr, 1ULL) - gbase;
-      s_item = v < (unsigned long long)(gtile * nlch) ? (long long)v : -1;
-    }
-    __syncthreads();  // also separates LDS use of consecutive items
-    const long long item = s_item;
-    if (item < 0) break;
-    int ch = (int)(item / gtile);  // lean chunk ordinal -> chunk index
-    for (int r = 0; r < a.nlzr; r++) {
-      const int n = a.lzr[r][1] - a.lzr[r][0] + 1;
-      if (ch < n) {
-        ch += a.lzr[r][0];
-        break;
-      }
-      ch -= n;
-    }
-    const int tile = (int)(gt0 + item % gtile);
-    const int tx = a.lx0 + tile % nlx, ty = a.ly0 + tile / nlx;
-    ItemGeo itg;
-    itg.x0 = a.xb[tx];
-    itg.x1 = a.xb[tx + 1] - 1;
-    itg.y0 = a.yb[ty] - 1;
-    itg.y1 = a.yb[ty + 1] - 1;
-    itg.zs = a.zb[ch];
-    itg.ze = a.zb[ch + 1];
-    const unsigned uw = (UMODE == 2 && a.uflag) ? a.uflag[(long long)tile * a.nch + ch] : ~0u;
-    lean_body<UMODE, DIST>(*kargs_opaque(), itg, uw, sU, sE, sB);
-  }
-}
-
-// Per lean item (tile t, chunk ch; grid ntile x nch): the palette word if every cell
-// of the item whose chi1inv the lean body uses -- its footprint (columns x0-1 ..
-// x0+FX, rows y0 .. y0+FR, planes zs-1 .. ze) inside the lean box L -- has the same
-// word, else ~0u (a word never has its top byte set).
-__global__ void lean_uniform_kernel(FusedArgs a, unsigned *flags) {
-  const int t = blockIdx.x, ch = blockIdx.y;
-  const int nlx = a.lx1 - a.lx0 + 1;
-  const int tx = a.lx0 + t % nlx, ty = a.ly0 + t / nlx;
-  const int x0 = max(a.xb[tx] - 1, a.L.lo[0]), x1 = min(a.xb[tx] + FX, a.L.hi[0]);
-  const int y0 = max(a.yb[ty] - 1, a.L.lo[1]), y1 = min(a.yb[ty] - 1 + FR, a.L.hi[1]);
-  const int z0 = max(a.zb[ch] - 1, a.L.lo[2]), z1 = min(a.zb[ch + 1], a.L.hi[2]);
+// The palette word shared by every cell of the box [x0, x1] x [y0, y1] x [z0, z1], or ~0u
+// where the cells differ (a word never has its top byte set); an empty box gives word 0.
+// Called by every thread of the workgroup, which all get the same value.
+__device__ unsigned uniform_word(const unsigned *uidx, long long st1, long long st2, int x0,
+                                 int x1, int y0, int y1, int z0, int z1) {
   __shared__ int bad;
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
   const long long nx = x1 - x0 + 1, ny = y1 - y0 + 1, nz = z1 - z0 + 1;
   unsigned ref = 0;
   if (nx > 0 && ny > 0 && nz > 0) {
-    ref = a.uidx[x0 + (long long)y0 * a.st1 + (long long)z0 * a.st2];
+    ref = uidx[x0 + (long long)y0 * st1 + (long long)z0 * st2];
     for (long long i = threadIdx.x; i < nx * ny * nz; i += blockDim.x) {
       const long long x = x0 + i % nx, y = y0 + (i / nx) % ny, z = z0 + i / (nx * ny);
-      if (a.uidx[x + y * a.st1 + z * a.st2] != ref) bad = 1;
+      if (uidx[x + y * st1 + z * st2] != ref) bad = 1;
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0) flags[(long long)t * a.nch + ch] = bad ? ~0u : ref;
+  return bad ? ~0u : ref;
 }
 
-// The same per general item (index in gitems): footprint columns x0-1 .. x0+TX, rows
-// y0 .. y0+R, planes zs-1 .. ze inside G (chi1inv is only used at owned points of G).
+// Per general item (index in gitems): the uniform palette word of its footprint (columns
+// x0-1 .. x0+GEN_TX, rows y0 .. y0+GEN_R, planes zs-1 .. ze) inside G, or ~0u (chi1inv is
+// only used at owned points of G).
 __global__ void general_uniform_kernel(FusedArgs a, unsigned *flags) {
   const int idx = blockIdx.x;
   const int item = a.gitems[idx];
-  const bool nar = item & (int)0x80000000u;
   const int tx = item & 255, ty = (item >> 8) & 255, ch = (item >> 16) & 255;
-  const int TX = nar ? 16 : 64, R = nar ? GenShape<16>::R : GenShape<64>::R;
-  const int yb = nar ? a.nyb[ty] : a.gyb[ty];
-  const int x0 = max(a.xb[tx] - 1, a.G.lo[0]), x1 = min(a.xb[tx] + TX, a.G.hi[0]);
-  const int y0 = max(yb - 1, a.G.lo[1]), y1 = min(yb - 1 + R, a.G.hi[1]);
+  const int x0 = max(a.xb[tx] - 1, a.G.lo[0]), x1 = min(a.xb[tx] + GEN_TX, a.G.hi[0]);
+  const int y0 = max(a.gyb[ty] - 1, a.G.lo[1]), y1 = min(a.gyb[ty] - 1 + GEN_R, a.G.hi[1]);
   const int z0 = max(a.zb[ch] - 1, a.G.lo[2]), z1 = min(a.zb[ch + 1], a.G.hi[2]);
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const long long nx = x1 - x0 + 1, ny = y1 - y0 + 1, nz = z1 - z0 + 1;
-  unsigned ref = 0;
-  if (nx > 0 && ny > 0 && nz > 0) {
-    ref = a.uidx[x0 + (long long)y0 * a.st1 + (long long)z0 * a.st2];
-    for (long long i = threadIdx.x; i < nx * ny * nz; i += blockDim.x) {
-      const long long x = x0 + i % nx, y = y0 + (i / nx) % ny, z = z0 + i / (nx * ny);
-      if (a.uidx[x + y * a.st1 + z * a.st2] != ref) bad = 1;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) flags[idx] = bad ? ~0u : ref;
+  const unsigned w = uniform_word(a.uidx, a.st1, a.st2, x0, x1, y0, y1, z0, z1);
+  if (threadIdx.x == 0) flags[idx] = w;
 }
 
 // chi1inv palette indices over box F: uidx[i] = idx0 | idx1 << 8 | idx2 << 16,
@@ -3744,23 +3614,15 @@ static void launch_general(const FusedArgs &g, int um, dim3 gr, dim3 b, hipStrea
     launch_general_u<0>(g, gr, b, s);
 }
 
-int k_lean_uniform(const FusedArgs &a, unsigned *flags, void *stream) {
-  const int ntile = (a.lx1 - a.lx0 + 1) * (a.ly1 - a.ly0 + 1);
-  if (ntile <= 0 || a.nch <= 0 || !a.uidx) return 0;
-  lean_uniform_kernel<<<dim3(ntile, a.nch), 256, 0, (hipStream_t)stream>>>(a, flags);
-  return rc();
-}
-
 int k_general_uniform(const FusedArgs &a, unsigned *flags, void *stream) {
   if (a.ngen <= 0 || !a.uidx || !a.gitems) return 0;
   general_uniform_kernel<<<a.ngen, 256, 0, (hipStream_t)stream>>>(a, flags);
   return rc();
 }
 
-// Per tile item (index in titems): the palette word if every cell of its footprint
-// (columns x0-1 .. x0+FX, rows y0 .. y0+FR, planes zs-1 .. ze; a narrow strip: columns
-// x0-1 .. x0+SW_N, rows y0 .. y0+SR_N) inside G has the same word, else ~0u (chi1inv is used
-// only at owned points of G).
+// Per tile item (index in titems): the uniform palette word of its footprint (columns
+// x0-1 .. x0+FX, rows y0 .. y0+FR, planes zs-1 .. ze; a narrow strip: columns x0-1 .. x0+SW_N,
+// rows y0 .. y0+SR_N) inside G, or ~0u (chi1inv is used only at owned points of G).
 __global__ void tile_uniform_kernel(FusedArgs a, unsigned *flags) {
   const int idx = blockIdx.x;
   const int item = a.titems[idx];
@@ -3783,20 +3645,8 @@ __global__ void tile_uniform_kernel(FusedArgs a, unsigned *flags) {
   const int x0 = max(ix0 - 1, a.G.lo[0]), x1 = min(ix0 + fw, a.G.hi[0]);
   const int y0 = max(iy0, a.G.lo[1]), y1 = min(iy0 + fr, a.G.hi[1]);
   const int z0 = max(izs - 1, a.G.lo[2]), z1 = min(ize, a.G.hi[2]);
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const long long nx = x1 - x0 + 1, ny = y1 - y0 + 1, nz = z1 - z0 + 1;
-  unsigned ref = 0;
-  if (nx > 0 && ny > 0 && nz > 0) {
-    ref = a.uidx[x0 + (long long)y0 * a.st1 + (long long)z0 * a.st2];
-    for (long long i = threadIdx.x; i < nx * ny * nz; i += blockDim.x) {
-      const long long x = x0 + i % nx, y = y0 + (i / nx) % ny, z = z0 + i / (nx * ny);
-      if (a.uidx[x + y * a.st1 + z * a.st2] != ref) bad = 1;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) flags[idx] = bad ? ~0u : ref;
+  const unsigned w = uniform_word(a.uidx, a.st1, a.st2, x0, x1, y0, y1, z0, z1);
+  if (threadIdx.x == 0) flags[idx] = w;
 }
 
 int k_tile_uniform(const FusedArgs &a, unsigned *flags, void *stream) {
@@ -3808,17 +3658,21 @@ int k_tile_uniform(const FusedArgs &a, unsigned *flags, void *stream) {
 int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bases) {
   for (int d = 0; d < 3; d++)
     if (a.G.hi[d] < a.G.lo[d]) return 0;
-  if (a.nelem * 8 >= (long long)MNL_OOB || !a.ctr) return 2;  // host guarantees < 4 GiB arrays
+  if (a.nelem * 8 >= (long long)MNL_OOB || !a.ctr || which < 1 || which > 6) return 2;
+  if (a.nx < 1 || a.nx > FUSED_MAXX || a.ny < 1 || a.ny > FUSED_MAXY || a.nch < 1 ||
+      a.nch > FUSED_MAXZ || a.ngy < 1 || a.ngy > FUSED_MAXGY)
+    return 3;
+  for (int t = 0; t < a.nx; t++)  // tiles at most 64 columns wide, 128-byte aligned
+    if (a.xb[t + 1] - a.xb[t] > FX || a.xb[t + 1] <= a.xb[t] || (a.xb[t] & 15)) return 4;
+  for (int t = 0; t < a.ny; t++)
+    if (a.yb[t + 1] - a.yb[t] > FOWN || a.yb[t + 1] <= a.yb[t]) return 5;
+  for (int t = 0; t < a.ngy; t++)
+    if (a.gyb[t + 1] - a.gyb[t] > FUSED_GW_ROWS || a.gyb[t + 1] <= a.gyb[t]) return 6;
+  for (int t = 0; t < a.nch; t++)
+    if (a.zb[t + 1] <= a.zb[t] || a.zb[t + 1] - a.zb[t] > FUSED_MAXCH) return 7;
+  hipStream_t s = (hipStream_t)stream;
+  const int um = a.uidx ? 2 : (a.u[0] ? 1 : 0);
   if (which >= 4) {  // tile kernel: 4 all items, 5 the chunk-0 items, 6 the others
-    if (a.nx < 1 || a.nx > FUSED_MAXX || a.ny < 1 || a.ny > FUSED_MAXY || a.nch < 1 ||
-        a.nch > FUSED_MAXZ)
-      return 3;
-    for (int t = 0; t < a.nx; t++)  // tiles at most 64 columns wide, 128-byte aligned
-      if (a.xb[t + 1] - a.xb[t] > FX || a.xb[t + 1] <= a.xb[t] || (a.xb[t] & 15)) return 4;
-    for (int t = 0; t < a.ny; t++)
-      if (a.yb[t + 1] - a.yb[t] > FOWN || a.yb[t + 1] <= a.yb[t]) return 5;
-    for (int t = 0; t < a.nch; t++)
-      if (a.zb[t + 1] <= a.zb[t] || a.zb[t + 1] - a.zb[t] > FUSED_MAXCH) return 7;
     int ib = 0, ie = a.ntit, line = 0;
     if (which == 5) ie = a.ntit_e, line = 1;
     if (which == 6) ib = a.ntit_e, line = 2;
@@ -3829,93 +3683,22 @@ int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bas
     FusedArgs t = a;
     t.gbeg = ib, t.gend = ie, t.ctr_line = line, t.cbase = bases[line];
     bases[line] += (unsigned long long)(ie - ib) + nb;
-    const int um = a.uidx ? 2 : (a.u[0] ? 1 : 0);
-    hipStream_t s = (hipStream_t)stream;
     launch_tile(t, um, dim3((unsigned)nb), s);
     return hipPeekAtLastError() == hipSuccess ? 0 : 9;
   }
-  if (a.nx < 1 || a.nx > FUSED_MAXX || a.ny < 0 || a.ny > FUSED_MAXY || a.nch < 1 ||
-      a.nch > FUSED_MAXZ || a.ngy < 1 || a.ngy > FUSED_MAXGY || a.nny < 0 || a.nny > FUSED_MAXNY)
-    return 3;
-  for (int t = 0; t < a.nx; t++)  // tiles at most 64 columns wide, 128-byte aligned
-    if (a.xb[t + 1] - a.xb[t] > FX || a.xb[t + 1] <= a.xb[t] || (a.xb[t] & 15)) return 4;
-  for (int t = 0; t < a.ny; t++)
-    if (a.yb[t + 1] - a.yb[t] > FOWN || a.yb[t + 1] <= a.yb[t]) return 5;
-  for (int t = 0; t < a.ngy; t++)
-    if (a.gyb[t + 1] - a.gyb[t] > FUSED_GW_ROWS || a.gyb[t + 1] <= a.gyb[t]) return 6;
-  for (int t = 0; t < a.nny; t++)
-    if (a.nyb[t + 1] - a.nyb[t] > FUSED_GN_ROWS || a.nyb[t + 1] <= a.nyb[t]) return 6;
-  for (int t = 0; t < a.nch; t++)
-    if (a.zb[t + 1] <= a.zb[t] || a.zb[t + 1] - a.zb[t] > FUSED_MAXCH) return 7;
-  hipStream_t s = (hipStream_t)stream;
-  const int um = a.uidx ? 2 : (a.u[0] ? 1 : 0);
-  if (which >= 1) {  // general tiles (both shapes, one launch)
-    // item range in a.gitems: [0, ngen); chunk-0 items lead ([0, ngen_e))
-    int ib = 0, ie = a.ngen, line = 8;
-    if (which == 2) ie = a.ngen_e, line = 10;
-    if (which == 3) ib = a.ngen_e;
-    long long cus = fused_grid_blocks(FUSED_GEN_BPC);
-    if (a.wg_limit > 0 && cus > a.wg_limit) cus = a.wg_limit;
-    if (ie > ib) {
-      FusedArgs g = a;
-      const unsigned nblk = (unsigned)std::min<long long>(cus, ie - ib);
-      g.gbeg = ib, g.gend = ie, g.ctr_line = line, g.cbase = bases[line];
-      const long long n = ie - ib;
-      g.ngrp = (a.ngrp_gen > 1 && nblk >= (unsigned)a.ngrp_gen && n >= 4LL * a.ngrp_gen) ? a.ngrp_gen : 1;
-      if (g.ngrp == 1) {
-        bases[line] += (unsigned long long)n + nblk;
-      } else {
-        for (int q = 0; q < g.ngrp; q++) {
-          const int L = FUSED_GLINE0 + (line - 8) * 8 + q;
-          g.cbg[q] = bases[L];
-          const long long items = n * (q + 1) / g.ngrp - n * q / g.ngrp;
-          const long long blocks = ((long long)nblk - q + g.ngrp - 1) / g.ngrp;
-          bases[L] += (unsigned long long)(items + blocks);
-        }
-      }
-      launch_general(g, um, dim3(nblk), dim3(64 * GEN_WAVES), s);
-    }
-    return hipPeekAtLastError() == hipSuccess ? 0 : 9;
+  // general tiles, item range in a.gitems: [0, ngen); chunk-0 items lead ([0, ngen_e))
+  int ib = 0, ie = a.ngen, line = 8;
+  if (which == 2) ie = a.ngen_e, line = 10;
+  if (which == 3) ib = a.ngen_e;
+  long long cus = fused_grid_blocks(FUSED_GEN_BPC);
+  if (a.wg_limit > 0 && cus > a.wg_limit) cus = a.wg_limit;
+  if (ie > ib) {
+    FusedArgs g = a;
+    const unsigned nblk = (unsigned)std::min<long long>(cus, ie - ib);
+    g.gbeg = ib, g.gend = ie, g.ctr_line = line, g.cbase = bases[line];
+    bases[line] += (unsigned long long)(ie - ib) + nblk;
+    launch_general(g, um, dim3(nblk), dim3(64 * GEN_WAVES), s);
   }
-  long long nlch = 0;
-  for (int r = 0; r < a.nlzr; r++) nlch += a.lzr[r][1] - a.lzr[r][0] + 1;
-  const bool anylean = a.lx1 >= a.lx0 && a.ly1 >= a.ly0 && nlch > 0;
-  const long long total = anylean ? (long long)(a.lx1 - a.lx0 + 1) * (a.ly1 - a.ly0 + 1) * nlch
-                                  : 0;
-  if (total == 0) return 0;
-  long long nb = fused_grid_blocks(a.blocks_per_cu > 0 ? a.blocks_per_cu : 1);
-  if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
-  if (nb > total) nb = total;
-  dim3 grd((unsigned)nb), blk(1024);
-  const bool d2 = a.dist == 2;
-  FusedArgs l = a;
-  const long long ntile = (long long)(a.lx1 - a.lx0 + 1) * (a.ly1 - a.ly0 + 1);
-  l.ngrp = (a.ngrp > 1 && ntile >= 4 * a.ngrp && nb >= a.ngrp) ? a.ngrp : 1;
-  l.cbase = bases[0];
-  if (l.ngrp == 1) {
-    bases[0] += (unsigned long long)total + nb;
-  } else {
-    for (int g = 0; g < l.ngrp; g++) {
-      l.cbg[g] = bases[g];
-      const long long tiles = ntile * (g + 1) / l.ngrp - ntile * g / l.ngrp;
-      const long long blocks = (nb - g + l.ngrp - 1) / l.ngrp;  // blockIdx % ngrp == g
-      bases[g] += (unsigned long long)(tiles * nlch + blocks);
-    }
-  }
-#define MNL_LAUNCH_FUSED(U)                                   \
-  do {                                                        \
-    if (d2)                                                   \
-      fused_kernel<U, 2><<<grd, blk, 0, s>>>(l);              \
-    else                                                      \
-      fused_kernel<U, 1><<<grd, blk, 0, s>>>(l);              \
-  } while (0)
-  if (um == 2)
-    MNL_LAUNCH_FUSED(2);
-  else if (um == 1)
-    MNL_LAUNCH_FUSED(1);
-  else
-    MNL_LAUNCH_FUSED(0);
-#undef MNL_LAUNCH_FUSED
   return hipPeekAtLastError() == hipSuccess ? 0 : 9;
 }
 
@@ -4382,25 +4165,16 @@ __global__ __launch_bounds__(1024) void tb2_kernel(TB2Args a) {
   }
 }
 
-// Per TB item: the palette word if every cell within distance 2 of its own box (the cells
-// whose chi1inv the two steps use) has the same word, else ~0u.
+// Per TB item: the uniform palette word of the cells within distance 2 of its own box (the
+// cells whose chi1inv the two steps use), or ~0u.
 __global__ void tb2_uniform_kernel(TB2Args a, unsigned *flags) {
   const int idx = blockIdx.x;
   const TB2Item it = a.items[idx];
   const int x0 = max((it.x & 0xFFFF) - 2, 0), x1 = min((it.x >> 16) + 2, a.N[0] - 1);
   const int y0 = max((it.y & 0xFFFF) - 2, 0), y1 = min((it.y >> 16) + 2, a.N[1] - 1);
   const int z0 = max((it.z & 0xFFFF) - 2, 0), z1 = min((it.z >> 16) + 1, a.N[2] - 1);
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const long long nx = x1 - x0 + 1, ny = y1 - y0 + 1, nz = z1 - z0 + 1;
-  const unsigned ref = a.uidx[x0 + (long long)y0 * a.st1 + (long long)z0 * a.st2];
-  for (long long i = threadIdx.x; i < nx * ny * nz; i += blockDim.x) {
-    const long long x = x0 + i % nx, y = y0 + (i / nx) % ny, z = z0 + i / (nx * ny);
-    if (a.uidx[x + y * a.st1 + z * a.st2] != ref) bad = 1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) flags[idx] = bad ? ~0u : ref;
+  const unsigned w = uniform_word(a.uidx, a.st1, a.st2, x0, x1, y0, y1, z0, z1);
+  if (threadIdx.x == 0) flags[idx] = w;
 }
 
 int k_tb2_uniform(const TB2Args &a, unsigned *flags, void *stream) {

@@ -194,9 +194,8 @@ def test_fused_many_distinct_chi1inv():
     _bitwise(p, sc_big_box_3d(make_oracle, steps=12, random_eps=True))
 
 
-@pytest.mark.parametrize("dist", ["1", "2"])
-def test_fused_prefetch_distance(monkeypatch, dist):
-    monkeypatch.setenv("MNL_FUSED_DIST", dist)
+def test_fused_prefetch_distance():
+    """The tile kernel's lean body prefetches one plane ahead (its only prefetch distance)."""
     _bitwise(sc_big_box_3d(ProductSim, steps=10), sc_big_box_3d(make_oracle, steps=10))
 
 

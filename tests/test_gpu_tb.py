@@ -111,6 +111,50 @@ def test_tb_interior_items_beside_previous_rim():
     _same(p, q)
 
 
+def sc_tb_lorentz(make, schedule=(), profile=False):
+    """sc_tb's grid with the dispersive slab of sc_big_lorentz_3d (1.0 < z < 3.0: chi1inv
+    1 / 2.25 and a Lorentzian) instead of the dielectric one: its z chunks are polarization
+    chunks (general kernel), the rest of the grid steps in pairs around them.  An Ex current a
+    few cells below the slab, random initial D / B."""
+    o = vol(make, 3, [9.6, 6.4, 8.0], 10, center_origin=True)
+    o.add_pml(0.7)
+    sig = []
+    for c in E_COMPS:
+        x, y, z = o.coords(c)
+        inside = (z > 1.0) & (z < 3.0)
+        o.set_chi1inv(c, c, np.where(inside, 1 / 2.25, 1.0))
+        sig.append(np.where(inside, 0.5, 0.0))
+    o.add_lorentzian(1.1, 0.05, sig)
+    o.add_gaussian_source(0, 0.3, 4.0, 0.0, 40.0, (0.05, 0.05, 0.65), 50.0)
+    random_init(o, (6, 7, 8, 9, 10, 11))
+    if isinstance(o, ProductSim):
+        for opt, val in schedule:
+            o._fields().set_schedule(opt, val)
+        if profile:
+            o._fields().set_profiling(True)
+    for n in (1, 10, 3, 1, 6):
+        o.step(n)
+    return o
+
+
+def test_tb_pairs_with_polarization_chunks():
+    """Pairs of steps around polarization chunks (schedule option tb_pol): the general kernel
+    steps those chunks one step at a time inside each pair.  Both the two-step kernel and the
+    general kernel ran, and the fields are bitwise the oracle and the same run with tb_pol
+    off (one step at a time: the general kernel's other caller)."""
+    p = sc_tb_lorentz(ProductSim, profile=True)
+    f = p._fields()
+    info = f.tb_info()
+    assert f.fused_active()
+    assert info["active"] and info["tb_pol"], info
+    assert f.kernel_stats(5)[0] >= 4  # pairs ran
+    assert f.kernel_stats(2)[0] > 0  # the general kernel ran
+    _same(p, sc_tb_lorentz(make_oracle))
+    q = sc_tb_lorentz(ProductSim, schedule=(("tb_pol", 0),))
+    assert not q._fields().tb_info()["active"]
+    _same(p, q)
+
+
 RETIRED = {"tb_px": 10, "tb_lint": 13, "r2_lpt": 14, "strip_zchunk": 15}
 # every surviving option with its default value (the run stays the default schedule)
 SURVIVING = {"narrow": 1, "dft_pal": 1, "res": -1, "res_tb2": -1, "res_rim": -1, "dft_cmp": 1,
