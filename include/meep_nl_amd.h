@@ -454,6 +454,26 @@ int mnl_fields_add_dft_fields(mnl_fields *f, int ncomp, const int *comps, const 
 int mnl_fields_dft_array(mnl_fields *f, int handle, int comp, int num_freq, int *rank,
                          long long dims[3], double *out, long long nout);
 
+/* ---- near-to-far-field monitors (src/near2far.cpp; meep.hpp dft_near2far) ----
+ * 3-D, non-periodic.  The DFT is accumulated like every other DFT object's
+ * (mnl_fields_dft_data, _dft_size, _dft_decimation, _dft_flush, _dft_array and
+ * dump / load work on the handle); the far-field transform runs on the device.
+ *
+ * fields::add_dft_near2far (src/near2far.cpp:558-642): regions as for
+ * mnl_fields_add_dft_flux (direction = the surface normal).  nperiods > 1 fails:
+ * periodic images need periodic boundaries. */
+int mnl_fields_add_dft_near2far(mnl_fields *f, int nreg, const double *regions, const double *freqs,
+                                int nfreq, int decimation, int nperiods, int *handle);
+/* dft_near2far::farfield for npts points (src/near2far.cpp:340-398), summed over ranks:
+ * out[npts][nfreq][6] complex (Ex,Ey,Ez,Hx,Hy,Hz; re/im interleaved) */
+int mnl_fields_near2far_farfields(mnl_fields *f, int handle, long long npts, const double *xyz,
+                                  double *out);
+/* eps, mu of the surrounding medium */
+int mnl_fields_near2far_medium(mnl_fields *f, int handle, double *eps, double *mu);
+/* per point of the list (the order of mnl_fields_dft_data): x, y, z, c0 (MNL_EX..MNL_HZ),
+ * weight (boundary weights * dV * sign * region weight); out[5 * points] */
+int mnl_fields_near2far_points(mnl_fields *f, int handle, double *out, long long npoints);
+
 #ifdef __cplusplus
 }
 #endif

@@ -712,6 +712,45 @@ class Fields:
             return np.zeros(0, dtype=np.complex128)
         return (out[0:2 * n:2] + 1j * out[1:2 * n:2]).reshape(shape)
 
+    # -- near2far (fields::add_dft_near2far / dft_near2far::farfield, src/near2far.cpp)
+    def add_dft_near2far(self, regions, freqs, decimation=0, nperiods=1):
+        """regions: [(min xyz, max xyz, normal direction, weight)]; returns a handle shared
+        with the other DFT objects (dft_data, dft_decimation, dft_array, dump / load)."""
+        r = np.ascontiguousarray([list(lo) + list(hi) + [d, w] for lo, hi, d, w in regions],
+                                 dtype=np.float64).ravel()
+        f = np.ascontiguousarray(freqs, dtype=np.float64)
+        h = ctypes.c_int()
+        check(lib().mnl_fields_add_dft_near2far(self.h, len(regions), ptr(r), ptr(f), len(f),
+                                                int(decimation), int(nperiods), ctypes.byref(h)))
+        self._dft_nf = getattr(self, "_dft_nf", {})
+        self._dft_nf[h.value] = len(f)
+        return h.value
+
+    def near2far_farfields(self, h, points):
+        """dft_near2far::farfield at every point (one batched call, the transform runs on the
+        GPU), summed over ranks: complex (npts, nfreq, 6) of Ex, Ey, Ez, Hx, Hy, Hz."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        nf = self._dft_nf.get(h, 1) if hasattr(self, "_dft_nf") else 1
+        out = np.zeros((len(p), nf, 12), dtype=np.float64)
+        check(lib().mnl_fields_near2far_farfields(self.h, h, len(p), ptr(p), ptr(out)))
+        return out[..., 0::2] + 1j * out[..., 1::2]
+
+    def near2far_points(self, h):
+        """Per point of the list (the order of dft_data(h, 0)): array (points, 5) of x, y, z,
+        the equivalent current's component c0 and the weight."""
+        n = ctypes.c_longlong()
+        check(lib().mnl_fields_dft_size(self.h, h, ctypes.byref(n)))
+        npts = n.value // self._dft_nf[h]
+        out = np.zeros((max(npts, 1), 5), dtype=np.float64)
+        check(lib().mnl_fields_near2far_points(self.h, h, ptr(out), npts))
+        return out[:npts]
+
+    def near2far_medium(self, h):
+        """(eps, mu) of the medium around the near2far surfaces."""
+        e, m = ctypes.c_double(), ctypes.c_double()
+        check(lib().mnl_fields_near2far_medium(self.h, h, ctypes.byref(e), ctypes.byref(m)))
+        return e.value, m.value
+
 
 class LocalHub:
     """In-process slab group (mnl_local_hub_create): several z-slabs of one grid on

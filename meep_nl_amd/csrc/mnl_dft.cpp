@@ -195,6 +195,8 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
             if (jc < g.owned_lo_sh[d] || jc > g.owned_hi_sh[d]) mine = false;
           }
           for (int d = 0; d < 3; d++) pj.push_back(mine ? j[d] : -1);
+          if (o.n2f)
+            for (int d = 0; d < 3; d++) o.h_pp.push_back(p[d]);
         }
     dc.p0 = o.h_pj.size() / 3;
     o.h_pj.insert(o.h_pj.end(), pj.begin(), pj.end());
@@ -374,6 +376,225 @@ int dft_add_fields(mnl_fields *F, int ncomp, const int *comps, const double wmin
   for (int k = 0; k < ncomp; k++)
     dft_add(F, *o, comps[k], wmin, wmax, false, cplx(1.0), dt_factor, o->E, pwE, yee != 0);
   return dft_layout(F, o, ho, pwE, pwH);
+}
+
+// ------------------------------------------------------------------ near2far
+// fields::get_eps / get_mu (src/monitor.cpp:202-224): the number of components over the
+// trace of the interpolated diagonal chi1inv at pos
+static double n2f_medium_at(const mnl_structure &S, int t, const double pos[3]) {
+  double tr = 0;
+  int nc = 0;
+  for (int k = 0; k < 3; k++) {
+    const int c = (t == T_E ? MNL_EX : MNL_HX) + k;
+    if (!has_field(S, c)) continue;
+    int locs[8][3];
+    double w[8];
+    interpolate(S, c, pos, locs, w);
+    double v = 0;
+    for (int i = 0; i < 8 && w[i]; i++) {
+      int j[3] = {0, 0, 0};
+      bool in = true;
+      for (int d = 0; d < 3; d++) {
+        if (!S.has[d]) continue;
+        const int h = locs[i][d] - S.io[d] - S.shift(c, d);
+        j[d] = h / 2;
+        if (h < 0 || j[d] > S.n[d]) in = false;
+      }
+      if (in) v += w[i] * mat_diag_at(S, t, k, j);
+    }
+    tr += v;
+    nc++;
+  }
+  return nc / tr;
+}
+
+static bool n2f_approxeq(double a, double b) { return fabs(a - b) < 0.5e-11 * (fabs(a) + fabs(b)); }
+
+// fields::add_dft_near2far (src/near2far.cpp:558-642): per region the two tangential E and the
+// two tangential H components on their own Yee grids with dV and interpolation weights, the
+// stored weight signed as n x field; every chunk in one list, with its equivalent current c0
+int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                     int decimation, int nperiods) {
+  if (F->src_dirty && build_source_lists(F)) return -1;
+  if (nreg < 1 || nfreq < 1) return fail("add_dft_near2far: no regions / frequencies");
+  const mnl_structure &S = F->S;
+  if (S.dim != 3) return fail("add_dft_near2far: 3-D only (no green2d / greencyl in this build)");
+  if (nperiods > 1)
+    return fail("add_dft_near2far: periodic near2far (nperiods > 1) needs periodic boundaries, "
+                "which this build does not have");
+  std::unique_ptr<DftFluxH> o(new DftFluxH);
+  o->fields = true;  // chunks in E only
+  o->n2f = true;
+  o->nfreq = nfreq;
+  for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]), o->freq.push_back(freqs[i]);
+  o->decim = dft_decimation(F, freqs, nfreq, decimation);
+  for (int d = 0; d < 3; d++) o->wmin[d] = regions[d], o->wmax[d] = regions[3 + d];
+  if (const char *e = getenv("MNL_DFT_BLOCK")) o->kb = std::max(1, std::min(DFT_KB, atoi(e)));
+  const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
+  std::vector<double> pw, pwH;
+  DftFluxH ho;
+  double eps = 0, mu = 0;
+  for (int r = 0; r < nreg; r++) {
+    const double *R = regions + 8 * r;
+    const int nd = int(R[6]);
+    const double wgt = R[7];
+    for (int d = 0; d < 3; d++) {  // everywhere = the union of the regions
+      o->wmin[d] = std::min(o->wmin[d], R[d]);
+      o->wmax[d] = std::max(o->wmax[d], R[3 + d]);
+    }
+    const double cen[3] = {0.5 * (R[0] + R[3]), 0.5 * (R[1] + R[4]), 0.5 * (R[2] + R[5])};
+    const double weps = n2f_medium_at(S, T_E, cen), wmu = n2f_medium_at(S, T_H, cen);
+    if (r > 0 && !(n2f_approxeq(eps, weps) && n2f_approxeq(mu, wmu)))
+      return fail("dft_near2far requires surfaces in a homogeneous medium");
+    eps = weps, mu = wmu;
+    const int fd[2] = {(nd + 1) % 3, (nd + 2) % 3};  // cyclic: the sign s below is that of n x c
+    for (int i = 0; i < 2; ++i)      // E or H
+      for (int j = 0; j < 2; ++j) {  // first or second component
+        const int c = (i == 0 ? MNL_EX : MNL_HX) + fd[j];
+        const int c0 = (i == 0 ? MNL_HX : MNL_EX) + fd[1 - j];
+        double s = j == 0 ? 1 : -1;
+        if (i == 0) s = -s;
+        const size_t before = o->E.size();
+        dft_add(F, *o, c, R, R + 3, true, cplx(s * wgt), dt_factor, o->E, pw, true);
+        for (size_t k = 0; k + before < o->E.size(); k++) o->E[k].c0 = c0;  // prepended
+      }
+  }
+  o->eps = eps, o->mu = mu;
+  o->h_pw = pw;
+  const int h = dft_layout(F, o, ho, pw, pwH);
+  if (h < 0) return -1;
+  DftFluxH &q = *F->dfts[h];
+  // Yee positions (IVEC_LOOP_LOC: half-pixel coordinate * 0.5 / a) and c0 in slot order
+  const size_t npad = (q.npts + 63) & ~size_t(63);
+  std::vector<double> x0(3 * npad, 0.0);
+  std::vector<int> sc0(q.npts, -1);
+  q.nmine = 0;
+  for (auto &dc : q.E)
+    for (size_t p = dc.p0; p < dc.p0 + dc.N; p++) {
+      const size_t t = q.slot[p];
+      sc0[t] = dc.c0;
+      for (int d = 0; d < 3; d++) x0[d * npad + t] = q.h_pp[3 * p + d] * (0.5 * (1.0 / S.a));
+      if (q.h_pj[3 * p] >= 0) q.nmine++;
+    }
+  std::vector<N2FRun> runs;
+  for (size_t t = 0; t < q.nmine; t++) {
+    if (runs.empty() || runs.back().c0 != sc0[t]) runs.push_back({(int)t, 0, sc0[t]});
+    runs.back().count++;
+  }
+  q.nruns = (int)runs.size();
+  // the split of the slots into workgroups depends on the object alone
+  const long long nblk = ((long long)q.nmine + 63) / 64;
+  q.n2f_wg_blocks = (int)std::max<long long>(N2F_WG_BLOCKS, (nblk + N2F_MAX_WG - 1) / N2F_MAX_WG);
+  q.n2f_nwg = (int)((nblk + q.n2f_wg_blocks - 1) / q.n2f_wg_blocks);
+  if (q.npts) {
+    if (dev_alloc(F, &q.d_x0, x0.size(), false) || dev_alloc(F, &q.d_freq, (size_t)nfreq, false) ||
+        dev_alloc(F, &q.d_runs, std::max<size_t>(runs.size(), 1), false))
+      return -1;
+    HIPCHK(hipMemcpyAsync(q.d_x0, x0.data(), x0.size() * 8, hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipMemcpyAsync(q.d_freq, q.freq.data(), (size_t)nfreq * 8, hipMemcpyHostToDevice,
+                          F->stream));
+    if (!runs.empty())
+      HIPCHK(hipMemcpyAsync(q.d_runs, runs.data(), runs.size() * sizeof(N2FRun),
+                            hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+  }
+  return h;
+}
+
+// per point of the list (the order of mnl_fields_dft_data): x, y, z, c0, weight
+int n2f_points(mnl_fields *F, int h, double *out, long long npoints) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  const DftFluxH &o = *F->dfts[h];
+  if (!o.n2f) return fail("near2far_points: the handle is not a near2far object");
+  long long k = 0;
+  for (auto &dc : o.E)
+    for (size_t p = dc.p0; p < dc.p0 + dc.N; p++, k++) {
+      if (k >= npoints) return fail("near2far_points: buffer too small");
+      for (int d = 0; d < 3; d++) out[5 * k + d] = o.h_pp[3 * p + d] * (0.5 * (1.0 / F->S.a));
+      out[5 * k + 3] = dc.c0;
+      out[5 * k + 4] = o.h_pw[p] * real(dc.stored);
+    }
+  return 0;
+}
+
+// dft_near2far::farfield (src/near2far.cpp:340-398) for npts points, summed over ranks:
+// out[npts][nfreq][6] complex.  Far points go through the kernels in batches that fit the
+// scratch buffer of partial sums; the batching does not change any point's result.
+int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  if (!o.n2f) return fail("near2far_farfields: the handle is not a near2far object");
+  if (npts < 0) return fail("near2far_farfields: negative point count");
+  const size_t per = (size_t)o.nfreq * 12;  // doubles per far point
+  for (size_t i = 0; i < (size_t)npts * per; i++) out[i] = 0.0;
+  std::string why;
+  bool ok = true;
+  const double t_start = wall_now();
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  auto run = [&]() -> int {
+    if (dft_flush(F, o)) return -1;  // the buffered updates first (same stream)
+    if (!o.nmine || !npts) return 0;
+    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    // batch: partial sums of at most 256 MiB, and the grid's z limit
+    const size_t cap = (size_t(256) << 20) / 8;
+    long long nb = std::max<size_t>(1, cap / ((size_t)o.n2f_nwg * per));
+    nb = std::min<long long>({nb, npts, 65535LL * N2F_NP});
+    if (o.n2f_part_cap < (size_t)o.n2f_nwg * nb * per || o.n2f_pts_cap < (size_t)nb) {
+      HIPCHK(hipStreamSynchronize(F->stream));
+      if (o.d_n2f_part) (void)hipFree(o.d_n2f_part);
+      if (o.d_n2f_xyz) (void)hipFree(o.d_n2f_xyz);
+      if (o.d_n2f_out) (void)hipFree(o.d_n2f_out);
+      o.d_n2f_part = o.d_n2f_xyz = o.d_n2f_out = nullptr;
+      o.n2f_part_cap = o.n2f_pts_cap = 0;
+      HIPCHK(hipMalloc(&o.d_n2f_part, (size_t)o.n2f_nwg * nb * per * 8));
+      HIPCHK(hipMalloc(&o.d_n2f_xyz, (size_t)nb * 3 * 8));
+      HIPCHK(hipMalloc(&o.d_n2f_out, (size_t)nb * per * 8));
+      o.n2f_part_cap = (size_t)o.n2f_nwg * nb * per;
+      o.n2f_pts_cap = (size_t)nb;
+    }
+    N2FArgs a{};
+    a.dft = o.d_dft, a.x0 = o.d_x0, a.runs = o.d_runs, a.nruns = o.nruns;
+    a.nslots = (long long)o.nmine, a.npad = (long long)((o.npts + 63) & ~size_t(63));
+    a.nfreq = o.nfreq, a.freq = o.d_freq, a.eps = o.eps, a.mu = o.mu;
+    a.xyz = o.d_n2f_xyz, a.wg_blocks = o.n2f_wg_blocks, a.part = o.d_n2f_part;
+    for (long long p0 = 0; p0 < npts; p0 += nb) {
+      const long long n = std::min(nb, npts - p0);
+      a.npts = (int)n;
+      HIPCHK(hipMemcpyAsync(o.d_n2f_xyz, xyz + 3 * p0, (size_t)n * 24, hipMemcpyHostToDevice,
+                            F->stream));
+      HIPCHK(hipEventRecord(ev[0], F->stream));
+      if (k_n2f_farfield(a, o.n2f_nwg, F->stream))
+        return fail("near2far farfield launch failed");
+      HIPCHK(hipEventRecord(ev[1], F->stream));
+      if (k_n2f_reduce(o.d_n2f_part, o.d_n2f_out, o.n2f_nwg, n * (long long)per, F->stream))
+        return fail("near2far reduce launch failed");
+      HIPCHK(hipEventRecord(ev[2], F->stream));
+      HIPCHK(hipMemcpyAsync(out + p0 * per, o.d_n2f_out, (size_t)n * per * 8,
+                            hipMemcpyDeviceToHost, F->stream));
+      HIPCHK(hipStreamSynchronize(F->stream));  // xyz and out are reused by the next batch
+      for (int k = 0; k < 2; k++) {  // kernel_stats 9 / 10
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        F->n2f_ms[k] += ms;
+        F->n2f_count[k]++;
+      }
+    }
+    return 0;
+  };
+  if (run()) ok = false, why = g_err;
+  for (auto &e : ev)
+    if (e) (void)hipEventDestroy(e);
+  F->sink_s[MNL_SINK_FARFIELDS] += wall_now() - t_start;  // GetFarfieldsTime
+  if (F->nranks > 1) {
+    if (F->comm->agree_ok(ok, F->stream))  // every rank fails together
+      return ok ? fail("near2far_farfields: a rank failed") : (g_err = why, -1);
+    const size_t tot = (size_t)npts * per;
+    for (size_t i0 = 0; i0 < tot; i0 += 64)  // sum_to_all
+      if (timed_allreduce(F, out + i0, (int)std::min<size_t>(64, tot - i0)))
+        return fail("near2far_farfields allreduce failed");
+  }
+  if (!ok) return g_err = why, -1;
+  return 0;
 }
 
 // phases of every DFT update in steps [t0+1, t0+ns] -> device (one row per update), after

@@ -5022,7 +5022,13 @@ void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
 
 int mnl_fields_kernel_stats(mnl_fields *F, int which, long long *launches, double *total_ms,
                             double *bytes_per_launch) {
-  if (!F || which < 0 || which > 8) return fail("bad kernel id");
+  if (!F || which < 0 || which > 10) return fail("bad kernel id");
+  if (which == 9 || which == 10) {  // near2far: the far-field kernel / the reduce kernel
+    *launches = F->n2f_count[which - 9];
+    *total_ms = F->n2f_ms[which - 9];
+    *bytes_per_launch = 0;
+    return 0;
+  }
   if (which == 7 || which == 8) {  // multi-rank pairs: slab-face chains / E-ghost waits
     const int cat = which == 7 ? TM_CHAIN : TM_WAIT;
     *launches = F->timer_count[cat];
@@ -5378,6 +5384,41 @@ int mnl_fields_dft_decimation(mnl_fields *F, int h, int *decimation) {
   if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
   *decimation = F->dfts[h]->decim;
   return 0;
+}
+
+int mnl_fields_add_dft_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs,
+                                int nfreq, int decimation, int nperiods, int *handle) {
+  if (!F || !regions || !freqs || !handle) return fail("null argument");
+  if (decimation < 0) return fail("decimation must be >= 0");
+  for (int r = 0; r < nreg; r++)
+    if (regions[8 * r + 6] < 0 || regions[8 * r + 6] > 2)
+      return fail("invalid normal direction in dft_near2far!");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  const int h = dft_add_near2far(F, nreg, regions, freqs, nfreq, decimation, nperiods);
+  if (h < 0) return -1;
+  *handle = h;
+  return 0;
+}
+
+int mnl_fields_near2far_farfields(mnl_fields *F, int h, long long npts, const double *xyz,
+                                  double *out) {
+  if (!F || (npts > 0 && (!xyz || !out))) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return n2f_farfields(F, h, npts, xyz, out);
+}
+
+int mnl_fields_near2far_medium(mnl_fields *F, int h, double *eps, double *mu) {
+  if (!F || !eps || !mu) return fail("null argument");
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (!F->dfts[h]->n2f) return fail("near2far_medium: the handle is not a near2far object");
+  *eps = F->dfts[h]->eps;
+  *mu = F->dfts[h]->mu;
+  return 0;
+}
+
+int mnl_fields_near2far_points(mnl_fields *F, int h, double *out, long long npoints) {
+  if (!F || !out) return fail("null argument");
+  return n2f_points(F, h, out, npoints);
 }
 
 int mnl_fields_traffic_model(mnl_fields *F, double *bpc, double *cells) {

@@ -192,6 +192,7 @@ struct DftChunkH {
   double s0[3], s1[3], e0[3], e1[3], dV0;
   bool incl;
   cplx stored;
+  int c0 = -1;       // near2far: the equivalent current's component (dft_chunk::vc)
 };
 struct DftFluxH {
   std::vector<double> omega;
@@ -230,7 +231,25 @@ struct DftFluxH {
   int *d_sci = nullptr;
   bool cmp_on = false;                // the current pair plan stores this monitor's box
   long long plan_key = -1;            // the mode the plan was built for (dft_plan_key)
+  // near2far (dft_near2far): every chunk is in E; per point the absolute
+  // half-pixel coordinates and the loop weight (reference order), on the device the Yee
+  // positions [3][slots padded to 64] and the (first slot, count, c0) runs in slot order
+  bool n2f = false;
+  double eps = 1, mu = 1;             // the surrounding medium
+  std::vector<double> freq;
+  std::vector<int> h_pp;
+  std::vector<double> h_pw;
+  double *d_x0 = nullptr, *d_freq = nullptr;
+  N2FRun *d_runs = nullptr;
+  int nruns = 0;
+  size_t nmine = 0;                   // this rank's slots (they sort first)
+  int n2f_nwg = 0, n2f_wg_blocks = 0; // the fixed split of the slots into workgroups
+  double *d_n2f_part = nullptr, *d_n2f_xyz = nullptr, *d_n2f_out = nullptr;  // farfields scratch
+  size_t n2f_part_cap = 0, n2f_pts_cap = 0;
   ~DftFluxH() {
+    if (d_n2f_part) (void)hipFree(d_n2f_part);
+    if (d_n2f_xyz) (void)hipFree(d_n2f_xyz);
+    if (d_n2f_out) (void)hipFree(d_n2f_out);
     if (d_ph) (void)hipFree(d_ph);
     if (d_sidx) (void)hipFree(d_sidx);
     if (d_ssel) (void)hipFree(d_ssel);
@@ -439,6 +458,8 @@ struct mnl_fields {
   long long last_out_t = 0;
   double timer_ms[16] = {0};
   long long timer_count[16] = {0};
+  double n2f_ms[2] = {0, 0};         // near2far: far-field kernel, reduce kernel (HIP events)
+  long long n2f_count[2] = {0, 0};
   std::vector<hipEvent_t> ev_pool;
   unsigned long long *d_nr_fallbacks = nullptr;
   NRHard *d_nr_hard = nullptr;      // deferred Newton-Raphson problems (NR runs only)
@@ -537,6 +558,7 @@ struct ZoneIv {
 };
 std::vector<ZoneIv> zone_intervals(const mnl_structure &S, int d);
 int build_source_lists(mnl_fields *F);
+void interpolate(const mnl_structure &S, int c, const double pc[3], int locs[8][3], double w[8]);
 
 // ---- mnl_dft.cpp: loop_in_chunks helpers and DFT monitors
 inline int my_round(double x) { return int(floor(fabs(x) + 0.5) * (x < 0 ? -1 : 1)); }
@@ -558,6 +580,10 @@ long long dft_plan_key(const mnl_fields *F);
 int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1);
 bool dft_due(const mnl_fields *F, long long t);
 int dft_flux_values(mnl_fields *F, int h, double *out);
+int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                     int decimation, int nperiods);
+int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out);
+int n2f_points(mnl_fields *F, int h, double *out, long long npoints);
 // ---- mnl_host.cpp, used by mnl_dft.cpp
 int timed_allreduce(mnl_fields *F, double *v, int n);
 
@@ -579,6 +605,7 @@ int fields_dump(mnl_fields *F, const char *path);
 int fields_load(mnl_fields *F, const char *path);
 int structure_dump(const mnl_structure *S, const char *path);
 int structure_load(mnl_structure *S, const char *path);
+double mat_diag_at(const mnl_structure &S, int t, int k, const int j[3]);
 int array_slice(mnl_fields *F, int c, const double vmin[3], const double vmax[3], int snap,
                 int *rank, long long dims[3], double *out, long long nout);
 int energy_in_box(mnl_fields *F, int which, const double wmin[3], const double wmax[3],

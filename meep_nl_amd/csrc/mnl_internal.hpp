@@ -560,4 +560,35 @@ int k_box_fill(double *dst, const DevGrid &g, int comp_type, int comp_dir, const
                const double *pos_hi, double value, int invert, double a, const int *io,
                void *stream);
 
+// dft_near2far::farfield_lowlevel (src/near2far.cpp:340-387) with green3d (133-187) for a batch
+// of far points: every workgroup sums its fixed range of this rank's slots for a tile of
+// frequencies and a block of far points into part[wg][far][freq][12]; k_n2f_reduce adds the
+// workgroups' partial sums in order
+constexpr int N2F_WAVES = 4;        // waves per workgroup
+constexpr int N2F_MAX_WG = 1024;    // slot ranges (workgroups along x) per object at most
+constexpr int N2F_WG_BLOCKS = 16;   // 64-slot blocks per slot range at least
+struct N2FRun {
+  int first, count, c0;  // slots [first, first + count) hold equivalent currents of component c0
+};
+struct N2FArgs {
+  const double *dft;     // [slot/64][freq][slot%64] complex
+  const double *x0;      // [3][npad] Yee positions in slot order
+  const N2FRun *runs;
+  int nruns;
+  long long nslots;      // this rank's slots (they sort first)
+  long long npad;        // slots rounded up to 64
+  int nfreq;
+  const double *freq;
+  double eps, mu;
+  const double *xyz;     // [npts][3] far points of this batch
+  int npts;
+  int wg_blocks;         // 64-slot blocks per workgroup (fixed per object)
+  double *part;          // [nwg][npts][nfreq][12]
+};
+// frequency tile x far-point block, by measurement (2x2 at 2 waves per
+// SIMD beat 4x2, 2x4 at 1 wave and 1x2 at 3 waves)
+constexpr int N2F_FT = 2, N2F_NP = 2;
+int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream);
+int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream);
+
 }  // namespace mnl

@@ -4752,6 +4752,169 @@ int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, in
   return rc();
 }
 
+// ------------------------------------------------- near-to-far-field transform
+// dft_near2far::farfield_lowlevel (src/near2far.cpp:340-387) for a block of NP far points and
+// a tile of FT frequencies over one workgroup's slot range.  Lanes are slots (the DFT array's
+// [slot/64][freq][slot%64] layout: coalesced 16-byte reads); x - x0, r and rhat are formed once
+// per (slot, far point) and every DFT value once per slot and frequency, so the sincos and the
+// green3d arithmetic dominate.  Each lane keeps its 12 doubles per (far point, frequency) in
+// registers over the whole slot range; one wave reduction and one LDS pass per workgroup at
+// the end.  The sums of one (far point, frequency) never depend on the other members of the
+// block or tile, so a far point's result is the same in every batch.
+__device__ __forceinline__ double n2f_wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+template <int FT, int NP>
+__global__ __launch_bounds__(64 * N2F_WAVES) void n2f_farfield_kernel(N2FArgs a) {
+  __shared__ double red[N2F_WAVES][NP * FT * 12];
+  constexpr double pi = 3.141592653589793238462643383276;  // meep::pi
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f0 = blockIdx.y * FT, p0 = blockIdx.z * NP;
+  const double n = sqrt(a.eps * a.mu), Z = sqrt(a.mu / a.eps);
+  double kk[FT], kinv[FT], ce[FT], cm[FT];
+#pragma unroll
+  for (int w = 0; w < FT; w++) {  // tail tiles repeat the last frequency (not written)
+    const double k = 2 * pi * a.freq[min(f0 + w, a.nfreq - 1)] * n;
+    kk[w] = k;
+    kinv[w] = 1.0 / k;
+    ce[w] = k * n / (4 * pi) / a.eps;
+    cm[w] = k * n / (4 * pi) / a.mu;
+  }
+  double X[NP][3];
+#pragma unroll
+  for (int q = 0; q < NP; q++)  // tail blocks repeat the last far point (not written)
+#pragma unroll
+    for (int d = 0; d < 3; d++) X[q][d] = a.xyz[3 * (long long)min(p0 + q, a.npts - 1) + d];
+  double acc[NP][FT][12];
+#pragma unroll
+  for (int q = 0; q < NP; q++)
+#pragma unroll
+    for (int w = 0; w < FT; w++)
+#pragma unroll
+      for (int j = 0; j < 12; j++) acc[q][w][j] = 0.0;
+  const long long nblk = (a.nslots + 63) >> 6;
+  const long long b0 = (long long)blockIdx.x * a.wg_blocks;
+  const long long b1 = min(b0 + (long long)a.wg_blocks, nblk);
+  const double2 *__restrict__ dft = reinterpret_cast<const double2 *>(a.dft);
+  for (long long b = b0 + wave; b < b1; b += N2F_WAVES) {
+    const long long s = b * 64 + lane;
+    if (s >= a.nslots) continue;  // the padded tail of the last block
+    // the run of this slot: c0 is uniform over long slot runs, so the two sides of the
+    // electric / magnetic choice below are wave-uniform except where a wave straddles two runs
+    int lo = 0, hi = a.nruns - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (a.runs[mid].first <= s)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    const int c0 = a.runs[lo].c0;
+    const bool elec = c0 < 3;
+    const int dir = c0 % 3;
+    const double px = dir == 0 ? 1.0 : 0.0, py = dir == 1 ? 1.0 : 0.0, pz = dir == 2 ? 1.0 : 0.0;
+    const double zf = elec ? 1.0 / Z : -Z;
+    const double x0 = a.x0[s], y0 = a.x0[a.npad + s], z0 = a.x0[2 * a.npad + s];
+    double rh[NP][3], rcp[NP][3], rinv[NP], rr[NP], pdr[NP];
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+      const double dx = X[q][0] - x0, dy = X[q][1] - y0, dz = X[q][2] - z0;
+      const double r = sqrt(dx * dx + dy * dy + dz * dz);
+      rr[q] = r;
+      rinv[q] = 1.0 / r;
+      rh[q][0] = dx / r, rh[q][1] = dy / r, rh[q][2] = dz / r;
+      pdr[q] = px * rh[q][0] + py * rh[q][1] + pz * rh[q][2];
+      rcp[q][0] = rh[q][1] * pz - rh[q][2] * py;
+      rcp[q][1] = rh[q][2] * px - rh[q][0] * pz;
+      rcp[q][2] = rh[q][0] * py - rh[q][1] * px;
+    }
+#pragma unroll
+    for (int w = 0; w < FT; w++) {
+      const double2 f = dft[(b * a.nfreq + min(f0 + w, a.nfreq - 1)) * 64 + lane];
+      const double cw = elec ? ce[w] : cm[w];
+#pragma unroll
+      for (int q = 0; q < NP; q++) {
+        double sn, cs;
+        sincos(kk[w] * rr[q] + pi * 0.5, &sn, &cs);
+        const double amp = cw * rinv[q];
+        const double pc = amp * cs, ps = amp * sn;
+        const double er = f.x * pc - f.y * ps, ei = f.x * ps + f.y * pc;  // expfac
+        const double inv = kinv[w] * rinv[q];  // 1 / (k r)
+        const double i2 = -(inv * inv);        // 1 / (i k r)^2
+        const double t1r = 1.0 + i2, t1i = inv;
+        const double t2r = (-1.0 - 3.0 * i2) * pdr[q], t2i = (-3.0 * inv) * pdr[q];
+        const double qr = (er - ei * inv) * zf, qi = (er * inv + ei) * zf;  // expfac * term3
+        double mn[6], cr[6];
+        const double pv[3] = {px, py, pz};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          const double mr = t1r * pv[j] + t2r * rh[q][j], mi = t1i * pv[j] + t2i * rh[q][j];
+          mn[2 * j] = er * mr - ei * mi;
+          mn[2 * j + 1] = er * mi + ei * mr;
+          cr[2 * j] = qr * rcp[q][j];
+          cr[2 * j + 1] = qi * rcp[q][j];
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+          acc[q][w][j] += elec ? mn[j] : cr[j];
+          acc[q][w][6 + j] += elec ? cr[j] : mn[j];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NP; q++)
+#pragma unroll
+    for (int w = 0; w < FT; w++)
+#pragma unroll
+      for (int j = 0; j < 12; j++) {
+        const double v = n2f_wave_sum(acc[q][w][j]);
+        if (lane == 0) red[wave][(q * FT + w) * 12 + j] = v;
+      }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < NP * FT * 12) {
+    const int q = t / (FT * 12), w = (t / 12) % FT, j = t % 12;
+    if (p0 + q < a.npts && f0 + w < a.nfreq) {
+      double v = red[0][t];
+#pragma unroll
+      for (int k = 1; k < N2F_WAVES; k++) v += red[k][t];
+      a.part[(((long long)blockIdx.x * a.npts + p0 + q) * a.nfreq + f0 + w) * 12 + j] = v;
+    }
+  }
+}
+
+// out[i] = the workgroups' partial sums of element i, added in workgroup order
+__global__ void __launch_bounds__(256)
+    n2f_reduce_kernel(const double *__restrict__ part, double *__restrict__ out, int nwg,
+                      long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v = 0.0;
+  for (int g = 0; g < nwg; g++) v += part[g * n + i];
+  out[i] = v;
+}
+
+int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream) {
+  if (a.npts <= 0 || nwg <= 0) return 0;
+  if (a.nfreq < 1 || a.nruns < 1 || a.wg_blocks < 1) return 2;
+  const dim3 grd((unsigned)nwg, (unsigned)((a.nfreq + N2F_FT - 1) / N2F_FT),
+                 (unsigned)((a.npts + N2F_NP - 1) / N2F_NP));
+  if (grd.y > 65535 || grd.z > 65535) return 2;
+  n2f_farfield_kernel<N2F_FT, N2F_NP><<<grd, dim3(64 * N2F_WAVES), 0, (hipStream_t)stream>>>(a);
+  return rc();
+}
+
+int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream) {
+  if (n <= 0) return 0;
+  n2f_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(part, out, nwg,
+                                                                                   n);
+  return rc();
+}
+
 int k_fill(double *p, double v, size_t n, void *stream) {
   if (n == 0) return 0;
   size_t blocks = (n + 255) / 256;

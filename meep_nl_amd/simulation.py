@@ -420,6 +420,102 @@ class DftFields:
                                                      self.yee_grid, self.decimation_factor)
 
 
+class Near2FarRegion(FluxRegion):
+    """python/simulation.py:640-684: a near-field surface and its normal direction
+    (AUTOMATIC: the one zero-size direction, volume::normal_direction)."""
+
+
+def farfield_grid(lo, hi, resolution):
+    """The points of dft_near2far::get_farfields_array (src/near2far.cpp:400-472) over
+    [lo, hi]: per direction dims = floor(size * resolution), a value <= 1 becomes 1, else
+    dx = size / (dims - 1).  Returns (points (N, 3) x-major, dims, dx)."""
+    dims, dx = [1, 1, 1], [0.0, 0.0, 0.0]
+    for d in range(3):
+        size = hi[d] - lo[d]
+        n = int(math.floor(size * resolution))
+        if n <= 1:
+            n = 1
+        else:
+            dx[d] = size / (n - 1)
+        dims[d] = n
+    ax = [lo[d] + np.arange(dims[d]) * dx[d] for d in range(3)]
+    g = np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3)
+    return g, dims, dx
+
+
+class DftNear2Far:
+    """python/simulation.py:811-905 (near2far object); the DFT lives on the GPU and the
+    far-field transform runs there (fields.near2far_farfields)."""
+
+    def __init__(self, sim, freq, regions, decimation_factor, nperiods):
+        self.sim = sim
+        self.freq = [float(f) for f in freq]
+        self.regions = list(regions)
+        self.decimation_factor = decimation_factor
+        self.nperiods = nperiods
+        self.handle = None
+
+    @property
+    def nfreqs(self):
+        return len(self.freq)
+
+    def _create(self):
+        sim = self.sim
+        regs = []
+        for r in self.regions:
+            if r.weight.imag != 0:
+                raise NotImplementedError("complex near2far weights are out of scope (real fields)")
+            d = _normal_direction(sim.dimensions, r.size) if r.direction < 0 else r.direction
+            lo = [r.center[k] - 0.5 * r.size[k] for k in range(3)]
+            hi = [r.center[k] + 0.5 * r.size[k] for k in range(3)]
+            regs.append((lo, hi, d, r.weight.real))
+        self.handle = sim.fields.add_dft_near2far(regs, self.freq, self.decimation_factor,
+                                                  self.nperiods)
+
+    @property
+    def eps(self):
+        return self.sim.fields.near2far_medium(self.handle)[0]
+
+    @property
+    def mu(self):
+        return self.sim.fields.near2far_medium(self.handle)[1]
+
+    def farfields_grid(self, lo, hi, resolution):
+        """complex (dims..., nfreq, 6) over the get_farfields_array grid: one batched call."""
+        pts, dims, dx = farfield_grid(lo, hi, resolution)
+        eh = self.sim.fields.near2far_farfields(self.handle, pts)
+        return eh.reshape(tuple(dims) + (len(self.freq), 6)), dims, dx
+
+    def flux(self, direction, where, resolution):
+        """dft_near2far::flux (src/near2far.cpp:506-554): the Poynting flux of the far
+        fields through `where` along direction, per frequency."""
+        lo = [where.center[k] - 0.5 * where.size[k] for k in range(3)]
+        hi = [where.center[k] + 0.5 * where.size[k] for k in range(3)]
+        eh, dims, dx = self.farfields_grid(lo, hi, resolution)
+        eh = eh.reshape(-1, len(self.freq), 6)
+        if direction == X:
+            ce, ch = (1, 2), (5, 4)
+        elif direction == Y:
+            ce, ch = (2, 0), (3, 5)
+        elif direction == Z:
+            ce, ch = (0, 1), (4, 3)
+        else:
+            raise RuntimeError("meep: invalid flux direction")
+        flux = np.zeros(len(self.freq))
+        for j in range(2):
+            flux += np.sum((eh[:, :, ce[j]] * np.conj(eh[:, :, ch[j]])).real, axis=0) * (1 - 2 * j)
+        dv = 1.0
+        for d in range(3):
+            if dims[d] > 1:
+                dv *= dx[d]
+        return list(flux * dv)
+
+
+def get_near2far_freqs(f):
+    """python/simulation.py:6030-6035"""
+    return list(f.freq)
+
+
 def get_flux_freqs(f):
     """python/simulation.py:6014-6019"""
     return list(f.freq)
@@ -1092,6 +1188,41 @@ class Simulation:
         self.dft_objects.append(flux)
         return flux
 
+    # -- near-to-far-field spectra (python/simulation.py:3073-3330)
+    def add_near2far(self, *args, **kwargs):
+        """add_near2far(fcen, df, nfreq, *Near2FarRegions, nperiods=1, decimation_factor=0) or
+        add_near2far(freq, *Near2FarRegions, ...) -> fields::add_dft_near2far
+        (src/near2far.cpp:558-642); initialises the fields first."""
+        args = fix_dft_args(args, 0)
+        freq, regions = args[0], args[1:]
+        n2f = DftNear2Far(self, freq, regions, kwargs.get("decimation_factor", 0),
+                          kwargs.get("nperiods", 1))
+        self.init_sim()
+        n2f._create()
+        self.dft_objects.append(n2f)
+        return n2f
+
+    def get_farfield(self, near2far, x):
+        """dft_near2far::farfield at x: 6 * nfreq complex values, frequency-major then
+        Ex, Ey, Ez, Hx, Hy, Hz (python/simulation.py:3246-3262)."""
+        eh = self.fields.near2far_farfields(near2far.handle, [[x[0], x[1], x[2]]])
+        return [complex(v) for v in eh[0].ravel()]
+
+    def get_farfields(self, near2far, resolution, where=None, center=None, size=None):
+        """The far fields on a grid of `resolution` points per unit length over a volume
+        (python/simulation.py:3264-3310 -> get_farfields_array, src/near2far.cpp:400-472): a
+        dict 'Ex'..'Hz' of complex arrays, singleton dimensions collapsed, frequency last
+        when nfreq > 1.  One batched transform on the GPU."""
+        if where is None and (center is None or size is None):
+            raise ValueError("Need either a Volume or a center and size Vector3")
+        lo, hi = self._where_bounds(where, center, size)
+        eh, dims, _ = near2far.farfields_grid(lo, hi, resolution)
+        shape = [n for n in dims if n > 1]
+        if len(near2far.freq) > 1:
+            shape.append(len(near2far.freq))
+        return {name: eh[..., k].reshape(shape)
+                for k, name in enumerate(("Ex", "Ey", "Ez", "Hx", "Hy", "Hz"))}
+
     def _where_bounds(self, where=None, center=None, size=None):
         """_volume_from_kwargs (python/simulation.py:2253-2262): where, else center +
         size, else the whole grid volume (fields::total_volume)."""
@@ -1135,7 +1266,7 @@ class Simulation:
         if not self.dft_objects:
             raise RuntimeError("DFT monitor dft_obj must be initialized before calling "
                                "get_dft_array")
-        if not isinstance(dft_obj, (DftFields, DftFlux)):
+        if not isinstance(dft_obj, (DftFields, DftFlux, DftNear2Far)):
             raise ValueError(f"Invalid type of dft object: {dft_obj}")
         return self.fields.dft_array(dft_obj.handle, int(component), int(num_freq))
 
