@@ -362,7 +362,9 @@ int mnl_fields_set_profiling(mnl_fields *f, int on);
  *            Lorentzian P), unfused mode; bytes 0 (not HBM-bound);
  * which = 5: temporal blocking: launches = pairs of
  *            steps, total_ms = every launch of the pairs, bytes per pair;
- * which = 6: rim launches that run alone (one step each). */
+ * which = 6: rim launches that run alone (one step each);
+ * which = 11, 12, 13: the gather, scatter and scale kernels of the DFT data calls
+ *            (mnl_fields_dft_get / _load / _scale), always timed; bytes of the last launch. */
 int mnl_fields_kernel_stats(mnl_fields *f, int which, long long *launches, double *total_ms,
                             double *bytes_per_launch);
 /* Temporal blocking (no reference counterpart: how this build steps pairs of
@@ -429,6 +431,35 @@ int mnl_fields_dft_size(mnl_fields *f, int handle, long long *n);
 int mnl_fields_dft_data(mnl_fields *f, int handle, int which, double *out, long long n);
 /* the decimation factor the object was created with */
 int mnl_fields_dft_decimation(mnl_fields *f, int handle, int *decimation);
+/* ---- DFT data of any DFT object (flux, dft-fields, near2far handles) ------
+ * The accumulated values of one chunk list (which 0: E, 1: H; dft-fields and near2far objects
+ * keep every chunk in list 0) in list order, [point][freq] complex, n complex values.  A rank
+ * holds the points it owns: get returns 0 for the others, load takes the full list and ignores
+ * them, so the full list is the sum over the ranks and data of a run on one GPU loads into a
+ * run on several.  Buffered updates are accumulated first.
+ *
+ * mnl_fields_dft_get: the array save_dft_hdf5 writes (src/dft.cpp:444-466; Python
+ * get_dft_data / get_flux_data / get_near2far_data, python/simulation.py:3067-3071, 3297,
+ * 3563), gathered on the device and copied for this list only; the same values as
+ * mnl_fields_dft_data.  n >= mnl_fields_dft_size. */
+int mnl_fields_dft_get(mnl_fields *f, int handle, int which, double *out, long long n);
+/* load_dft_hdf5 (src/dft.cpp:468-496; Python load_flux_data / load_minus_flux_data /
+ * load_near2far_data, python/simulation.py:3305-3355, 3575-3635): the list's values become
+ * sign * in, sign = +-1 (-1: load followed by scale_dfts(-1) in one pass).  n must equal
+ * mnl_fields_dft_size: "incorrect dataset size (%zd vs. %zd) in load_dft..." otherwise. */
+int mnl_fields_dft_load(mnl_fields *f, int handle, int which, const double *in, long long n,
+                        int sign);
+/* dft_flux::scale_dfts / dft_fields::scale_dfts / dft_near2far::scale_dfts (src/dft.cpp:573-576,
+ * 879; dft_chunk::scale_dft 401-405; Python scale_flux_fields / scale_near2far_fields,
+ * python/simulation.py:5997, 6058): every value of every list times re + i im. */
+int mnl_fields_dft_scale(mnl_fields *f, int handle, double re, double im);
+/* dft_flux::save_hdf5 / load_hdf5, dft_near2far::save_hdf5 / load_hdf5 (Python save_flux /
+ * load_flux / load_minus_flux, save_near2far / ...): a flat binary file (no HDF5 here) with a
+ * magic, the number of lists, nfreq, the frequencies, the points per list and the lists in
+ * list order.  Collective on several ranks: rank 0 writes the assembled lists, every rank
+ * reads the file.  Loading checks the magic, nfreq and the sizes, not the frequencies. */
+int mnl_fields_dft_save(mnl_fields *f, int handle, const char *filename);
+int mnl_fields_dft_load_file(mnl_fields *f, int handle, const char *filename, int sign);
 /* Accumulate every buffered DFT update now and wait for the device (no reference
  * counterpart: the reference adds each update to the DFT array in fields::update_dfts,
  * src/dft.cpp:249-263; this build samples every update and adds up to 32 of them per pass

@@ -13,6 +13,7 @@ from .simulation import (ALL, AUTOMATIC, Block, ContinuousSource, CustomSource, 
                          PML, Simulation, Source, Vector3, Volume, after_sources, after_time,
                          air, at_beginning, at_end, at_every, before_time, combine_step_funcs,
                          during_sources, get_flux_freqs, get_fluxes, get_near2far_freqs, inf, stop_after_walltime,
+                         FluxData, NearToFarData, scale_flux_fields, scale_near2far_fields,
                          stop_when_fields_decayed, vacuum, when_false, when_true, verbosity,
                          quiet, wall_time)
 

@@ -105,6 +105,11 @@ _SIGS = {
     "mnl_fields_dft_size": (c_int, [c_void, c_int, llptr]),
     "mnl_fields_dft_data": (c_int, [c_void, c_int, c_int, dptr, ctypes.c_longlong]),
     "mnl_fields_dft_decimation": (c_int, [c_void, c_int, iptr]),
+    "mnl_fields_dft_get": (c_int, [c_void, c_int, c_int, dptr, ctypes.c_longlong]),
+    "mnl_fields_dft_load": (c_int, [c_void, c_int, c_int, dptr, ctypes.c_longlong, c_int]),
+    "mnl_fields_dft_scale": (c_int, [c_void, c_int, c_double, c_double]),
+    "mnl_fields_dft_save": (c_int, [c_void, c_int, ctypes.c_char_p]),
+    "mnl_fields_dft_load_file": (c_int, [c_void, c_int, ctypes.c_char_p, c_int]),
     "mnl_fields_dft_flush": (c_int, [c_void]),
     "mnl_fields_set_time": (c_int, [c_void, ctypes.c_longlong]),
     "mnl_fields_zero_fields": (c_int, [c_void]),

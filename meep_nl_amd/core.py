@@ -668,6 +668,38 @@ class Fields:
         check(lib().mnl_fields_dft_data(self.h, h, int(which), ptr(out), n.value))
         return out[0::2] + 1j * out[1::2]
 
+    # -- DFT data of any DFT object (save_dft_hdf5 / load_dft_hdf5 / scale_dft, src/dft.cpp:401-496)
+    def dft_get(self, h, which=0):
+        """The values dft_data returns, gathered into list order on the GPU and copied for
+        this list only (mnl_fields_dft_get); points another rank owns read 0."""
+        n = ctypes.c_longlong()
+        check(lib().mnl_fields_dft_size(self.h, h, ctypes.byref(n)))
+        out = np.zeros(2 * n.value, dtype=np.float64)
+        check(lib().mnl_fields_dft_get(self.h, h, int(which), ptr(out), n.value))
+        return out.view(np.complex128)
+
+    def dft_load(self, h, which, data, sign=1):
+        """The list's values become sign * data (sign +-1; load_dft_hdf5, and with -1 the
+        reference's load followed by scale_dfts(-1)).  data is the full list on every rank;
+        a rank keeps the points it owns."""
+        d = np.ascontiguousarray(data, dtype=np.complex128).ravel()
+        check(lib().mnl_fields_dft_load(self.h, h, int(which), ptr(d.view(np.float64)), d.size,
+                                        int(sign)))
+
+    def dft_scale(self, h, s):
+        """Every value of every list of the object times the complex s (scale_dfts)."""
+        s = complex(s)
+        check(lib().mnl_fields_dft_scale(self.h, h, s.real, s.imag))
+
+    def dft_save(self, h, fname):
+        """The object's lists to a flat binary file (collective: rank 0 writes the lists
+        assembled over the ranks)."""
+        check(lib().mnl_fields_dft_save(self.h, h, os.fsencode(fname)))
+
+    def dft_load_file(self, h, fname, sign=1):
+        """sign * the lists of a dft_save file into this object (every rank reads the file)."""
+        check(lib().mnl_fields_dft_load_file(self.h, h, os.fsencode(fname), int(sign)))
+
     def dft_flush(self):
         """Accumulate every buffered DFT update now and wait for the device
         (mnl_fields_dft_flush; readers flush by themselves, updates stay buffered between

@@ -810,4 +810,118 @@ int dft_flux_values(mnl_fields *F, int h, double *out) {
   return 0;
 }
 
+// ------------------------------------------------------------------ DFT data
+// get / load / scale of the accumulated values in list order, replacing
+// save_dft_hdf5 / load_dft_hdf5 (src/dft.cpp:444-496) and dft_chunk::scale_dft (401-405).
+size_t dft_list_points(const DftFluxH &o, int which) {
+  size_t n = 0;
+  for (auto &dc : which ? o.H : o.E) n += dc.N;
+  return n;
+}
+
+// the per-slot inverse map of one list (built and uploaded at its first use) and a device
+// buffer for the list's values
+static int dft_list_ready(mnl_fields *F, DftFluxH &o, int which) {
+  const size_t npad = (o.npts + 63) & ~size_t(63);
+  if (!o.d_inv[which] && npad) {
+    std::vector<int> inv(npad, -1);
+    int k = 0;
+    for (auto &dc : which ? o.H : o.E)
+      for (size_t p = dc.p0; p < dc.p0 + dc.N; p++, k++)
+        if (o.h_pj[3 * p] >= 0) inv[o.slot[p]] = k;
+    HIPCHK(hipMalloc(&o.d_inv[which], npad * 4));
+    HIPCHK(hipMemcpyAsync(o.d_inv[which], inv.data(), npad * 4, hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));  // inv leaves scope
+  }
+  const size_t need = 2 * dft_list_points(o, which) * (size_t)o.nfreq;
+  if (o.list_cap < need) {
+    HIPCHK(hipStreamSynchronize(F->stream));
+    if (o.d_list) (void)hipFree(o.d_list);
+    o.d_list = nullptr, o.list_cap = 0;
+    HIPCHK(hipMalloc(&o.d_list, need * 8));
+    o.list_cap = need;
+  }
+  return 0;
+}
+
+// one kernel between two events -> kernel_stats 11 (gather), 12 (scatter), 13 (scale)
+template <class Fn>
+static int dft_io_timed(mnl_fields *F, int id, double bytes, Fn launch) {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  auto run = [&]() -> int {
+    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ev[0], F->stream));
+    if (launch()) return fail("dft data kernel launch failed");
+    HIPCHK(hipEventRecord(ev[1], F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    F->dftio_ms[id] += ms;
+    F->dftio_count[id]++;
+    F->dftio_bytes[id] = bytes;
+    return 0;
+  };
+  const int r = run();
+  for (auto &e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return r;
+}
+
+int dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (which != 0 && which != 1) return fail("dft_get: which must be 0 (E) or 1 (H)");
+  DftFluxH &o = *F->dfts[h];
+  const size_t nl = dft_list_points(o, which) * (size_t)o.nfreq;  // complex values
+  if (n < 0 || (size_t)n < nl) return fail("dft buffer too small");
+  if (dft_flush(F, o)) return -1;  // the buffered updates first (same stream)
+  for (size_t i = 2 * nl; i < 2 * (size_t)n; i++) out[i] = 0.0;
+  if (!nl) return 0;
+  if (dft_list_ready(F, o, which)) return -1;
+  HIPCHK(hipMemsetAsync(o.d_list, 0, nl * 16, F->stream));  // other ranks' points read 0
+  const size_t npad = (o.npts + 63) & ~size_t(63);
+  if (dft_io_timed(F, 0, 16.0 * nl + 16.0 * o.nfreq * npad + 4.0 * npad, [&]() {
+        return k_dft_gather(o.d_dft, o.d_inv[which], o.d_list, o.nfreq, (long long)npad, F->stream);
+      }))
+    return -1;
+  HIPCHK(hipMemcpyAsync(out, o.d_list, nl * 16, hipMemcpyDeviceToHost, F->stream));
+  HIPCHK(hipStreamSynchronize(F->stream));
+  return 0;
+}
+
+int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (which != 0 && which != 1) return fail("dft_load: which must be 0 (E) or 1 (H)");
+  if (sign != 1 && sign != -1) return fail("dft_load: sign must be 1 or -1");
+  DftFluxH &o = *F->dfts[h];
+  const size_t nl = dft_list_points(o, which) * (size_t)o.nfreq;
+  if (n < 0 || (size_t)n != nl) {
+    char b[160];  // load_dft_hdf5 (src/dft.cpp:482-484), sizes in doubles as there
+    snprintf(b, sizeof b, "incorrect dataset size (%lld vs. %lld) in load_dft %d:%s",
+             (long long)(2 * n), (long long)(2 * nl), h, which ? "H" : "E");
+    return fail(b);
+  }
+  // the updates sampled before the load belong to the values it replaces: accumulate them
+  // now (nbuf = 0, no phase row carried over), then overwrite this list
+  if (dft_flush(F, o)) return -1;
+  if (!nl) return 0;
+  if (dft_list_ready(F, o, which)) return -1;
+  HIPCHK(hipMemcpyAsync(o.d_list, in, nl * 16, hipMemcpyHostToDevice, F->stream));
+  const size_t npad = (o.npts + 63) & ~size_t(63);
+  return dft_io_timed(F, 1, 32.0 * nl + 4.0 * npad, [&]() {
+    return k_dft_scatter(o.d_dft, o.d_inv[which], o.d_list, (double)sign, o.nfreq,
+                         (long long)npad, F->stream);
+  });
+}
+
+int dft_scale(mnl_fields *F, int h, double re, double im) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  if (dft_flush(F, o)) return -1;  // everything accumulated so far is scaled
+  const size_t nc = ((o.npts + 63) & ~size_t(63)) * (size_t)o.nfreq;
+  if (!nc) return 0;
+  return dft_io_timed(F, 2, 32.0 * nc, [&]() {
+    return k_dft_scale(o.d_dft, re, im, (long long)nc, F->stream);
+  });
+}
+
 }  // namespace mnlh

@@ -5022,7 +5022,13 @@ void fused_bytes(const mnl_fields *F, double *lean_bytes, double *gen_bytes) {
 
 int mnl_fields_kernel_stats(mnl_fields *F, int which, long long *launches, double *total_ms,
                             double *bytes_per_launch) {
-  if (!F || which < 0 || which > 10) return fail("bad kernel id");
+  if (!F || which < 0 || which > 13) return fail("bad kernel id");
+  if (which >= 11) {  // DFT data: the gather / scatter / scale kernels
+    *launches = F->dftio_count[which - 11];
+    *total_ms = F->dftio_ms[which - 11];
+    *bytes_per_launch = F->dftio_bytes[which - 11];
+    return 0;
+  }
   if (which == 9 || which == 10) {  // near2far: the far-field kernel / the reduce kernel
     *launches = F->n2f_count[which - 9];
     *total_ms = F->n2f_ms[which - 9];
@@ -5377,6 +5383,36 @@ int mnl_fields_dft_data(mnl_fields *F, int h, int which, double *out, long long 
         out[k++] = v[2 * dft_at(o.slot[dc.p0 + p], i, nf) + 1];
       }
   return 0;
+}
+
+int mnl_fields_dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
+  if (!F || !out) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_get(F, h, which, out, n);
+}
+
+int mnl_fields_dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign) {
+  if (!F || (n > 0 && !in)) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_load(F, h, which, in, n, sign);
+}
+
+int mnl_fields_dft_scale(mnl_fields *F, int h, double re, double im) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_scale(F, h, re, im);
+}
+
+int mnl_fields_dft_save(mnl_fields *F, int h, const char *filename) {
+  if (!F || !filename) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_save(F, h, filename);
+}
+
+int mnl_fields_dft_load_file(mnl_fields *F, int h, const char *filename, int sign) {
+  if (!F || !filename) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_load_file(F, h, filename, sign);
 }
 
 int mnl_fields_dft_decimation(mnl_fields *F, int h, int *decimation) {

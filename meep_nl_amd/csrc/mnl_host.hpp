@@ -246,7 +246,15 @@ struct DftFluxH {
   int n2f_nwg = 0, n2f_wg_blocks = 0; // the fixed split of the slots into workgroups
   double *d_n2f_part = nullptr, *d_n2f_xyz = nullptr, *d_n2f_out = nullptr;  // farfields scratch
   size_t n2f_part_cap = 0, n2f_pts_cap = 0;
+  // data in list order: per list the slot -> list index map (-1: not in
+  // the list or not this rank's; built at first use) and a device buffer [list point][freq]
+  int *d_inv[2] = {nullptr, nullptr};
+  double *d_list = nullptr;
+  size_t list_cap = 0;                // doubles
   ~DftFluxH() {
+    if (d_inv[0]) (void)hipFree(d_inv[0]);
+    if (d_inv[1]) (void)hipFree(d_inv[1]);
+    if (d_list) (void)hipFree(d_list);
     if (d_n2f_part) (void)hipFree(d_n2f_part);
     if (d_n2f_xyz) (void)hipFree(d_n2f_xyz);
     if (d_n2f_out) (void)hipFree(d_n2f_out);
@@ -460,6 +468,9 @@ struct mnl_fields {
   long long timer_count[16] = {0};
   double n2f_ms[2] = {0, 0};         // near2far: far-field kernel, reduce kernel (HIP events)
   long long n2f_count[2] = {0, 0};
+  double dftio_ms[3] = {0, 0, 0};    // DFT data: gather, scatter, scale kernels (HIP events)
+  long long dftio_count[3] = {0, 0, 0};
+  double dftio_bytes[3] = {0, 0, 0}; // algorithmic bytes of the last launch
   std::vector<hipEvent_t> ev_pool;
   unsigned long long *d_nr_fallbacks = nullptr;
   NRHard *d_nr_hard = nullptr;      // deferred Newton-Raphson problems (NR runs only)
@@ -580,6 +591,12 @@ long long dft_plan_key(const mnl_fields *F);
 int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1);
 bool dft_due(const mnl_fields *F, long long t);
 int dft_flux_values(mnl_fields *F, int h, double *out);
+size_t dft_list_points(const DftFluxH &o, int which);
+int dft_get(mnl_fields *F, int h, int which, double *out, long long n);
+int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign);
+int dft_scale(mnl_fields *F, int h, double re, double im);
+int dft_save(mnl_fields *F, int h, const char *path);
+int dft_load_file(mnl_fields *F, int h, const char *path, int sign);
 int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
                      int decimation, int nperiods);
 int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out);

@@ -481,6 +481,13 @@ int k_dft_sample_jobs(const DftSampleJobs &J, const DevGrid &g, const DevFields 
                       const double *utab, void *stream);
 int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, int n,
                 const double *ph, long long rstride, int nfreq, long long npts, void *stream);
+// DFT data in list order: inv[slot] = index in the list or -1, for
+// nslots padded to 64; out / in are [list point][freq] complex on the device
+int k_dft_gather(const double *dft, const int *inv, double *out, int nfreq, long long nslots,
+                 void *stream);
+int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, int nfreq,
+                  long long nslots, void *stream);
+int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream);
 int k_init_add(double *dst, double *alt, const double *src, const DevGrid &g, const DevFields &f,
                int comp_type, int comp_dir, void *stream);
 int k_copy(double *dst, const double *src, long long n, void *stream);

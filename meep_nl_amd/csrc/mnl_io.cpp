@@ -1,6 +1,7 @@
-// mnl_io.cpp -- checkpoints (fields::dump / load, structure::dump / load), array slices
-// (fields::get_array_slice, src/array_slice.cpp) and field energy (fields::field_energy_in_box,
-// src/energy_and_flux.cpp) of the MI355X fields (DESIGN.md sections 13, 15, 18).
+// mnl_io.cpp -- checkpoints (fields::dump / load, structure::dump / load), DFT data files
+// (DESIGN.md section 29), array slices (fields::get_array_slice, src/array_slice.cpp) and field
+// energy (fields::field_energy_in_box, src/energy_and_flux.cpp) of the MI355X fields (DESIGN.md
+// sections 13, 15, 18).
 #include "mnl_host.hpp"
 
 namespace mnlh {
@@ -145,6 +146,98 @@ int fields_load(mnl_fields *F, const char *path) {
   // already separate (a dump taken before the first step holds zeros in them)
   F->e_first_done = F->h_first_done = true;
   F->u_first_done[0] = F->u_first_done[1] = true;
+  return 0;
+}
+
+// ------------------------------------------------------------- DFT data files
+// Flat binary file (no HDF5 in this build; save_dft_hdf5 / load_dft_hdf5, src/dft.cpp:444-496):
+// magic, number of lists, nfreq, the frequencies, the points per list, then every list's
+// values in list order.  Rank 0 writes the lists assembled over the ranks (every point has one
+// owner, so the sum is exact); every rank reads the whole file and keeps its own points.
+static constexpr char DD_MAGIC[8] = {'M', 'N', 'L', 'D', 'F', 'T', '0', '1'};
+
+int dft_save(mnl_fields *F, int h, const char *path) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  const int nlists = o.H.empty() ? 1 : 2;
+  std::vector<std::vector<double>> data(nlists);
+  bool ok = true;
+  std::string why;
+  for (int w = 0; w < nlists && ok; w++) {
+    const size_t nl = dft_list_points(o, w) * (size_t)o.nfreq;
+    data[w].assign(2 * nl, 0.0);
+    if (dft_get(F, h, w, data[w].data(), (long long)nl)) ok = false, why = g_err;
+  }
+  if (F->nranks > 1) {
+    if (F->comm->agree_ok(ok, F->stream))  // every rank fails together
+      return ok ? fail("dft_save: a rank failed") : (g_err = why, -1);
+    for (auto &v : data)
+      for (size_t q = 0; q < v.size(); q += 1 << 20)  // sum_to_all in pieces
+        if (timed_allreduce(F, v.data() + q, (int)std::min<size_t>(1 << 20, v.size() - q)))
+          return fail("dft_save allreduce failed");
+  }
+  if (!ok) return g_err = why, -1;
+  if (F->rank == 0) {
+    FILE *fp = fopen(path, "wb");
+    if (!fp) ok = false, why = std::string("meep: cannot create dft output file ") + path;
+    if (fp) {
+      std::unique_ptr<FILE, int (*)(FILE *)> guard(fp, fclose);
+      const int32_t hd[2] = {nlists, o.nfreq};
+      bool w = fwrite(DD_MAGIC, 8, 1, fp) == 1 && fwrite(hd, sizeof hd, 1, fp) == 1;
+      for (int i = 0; i < o.nfreq && w; i++) {
+        const double fr = o.omega[i] / (2 * pi);
+        w = fwrite(&fr, 8, 1, fp) == 1;
+      }
+      for (int l = 0; l < nlists && w; l++) {
+        const uint64_t np = dft_list_points(o, l);
+        w = fwrite(&np, 8, 1, fp) == 1;
+      }
+      for (int l = 0; l < nlists && w; l++)
+        w = data[l].empty() || fwrite(data[l].data(), 8, data[l].size(), fp) == data[l].size();
+      if (!w || fflush(fp)) ok = false, why = "meep: dft_save: write error";
+    }
+  }
+  if (F->nranks > 1 && F->comm->agree_ok(ok, F->stream))  // the file is complete on return
+    return ok ? fail("dft_save: rank 0 could not write the file") : (g_err = why, -1);
+  if (!ok) return g_err = why, -1;
+  return 0;
+}
+
+int dft_load_file(mnl_fields *F, int h, const char *path, int sign) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (sign != 1 && sign != -1) return fail("dft_load_file: sign must be 1 or -1");
+  DftFluxH &o = *F->dfts[h];
+  FILE *fp = fopen(path, "rb");
+  if (!fp) return fail(std::string("cannot open dft file ") + path);
+  std::unique_ptr<FILE, int (*)(FILE *)> guard(fp, fclose);
+  char magic[8];
+  int32_t hd[2];
+  if (fread(magic, 8, 1, fp) != 1 || memcmp(magic, DD_MAGIC, 8) || fread(hd, sizeof hd, 1, fp) != 1)
+    return fail(std::string("not a dft data file: ") + path);
+  const int nlists = o.H.empty() ? 1 : 2;
+  if (hd[0] != nlists || hd[1] < 1) return fail("dft file holds a different kind of dft object");
+  std::vector<double> fr(hd[1]);  // read, not compared value for value (as the reference)
+  uint64_t np[2] = {0, 0};
+  if (fread(fr.data(), 8, fr.size(), fp) != fr.size() || fread(np, 8, nlists, fp) != (size_t)nlists)
+    return fail("dft file: read error (truncated file)");
+  for (int l = 0; l < nlists; l++) {
+    const size_t file_n = 2 * (size_t)np[l] * (size_t)hd[1];
+    const size_t n = 2 * dft_list_points(o, l) * (size_t)o.nfreq;
+    if (file_n != n) {
+      char b[200];
+      snprintf(b, sizeof b, "incorrect dataset size (%lld vs. %lld) in load_dft %s:%s",
+               (long long)file_n, (long long)n, path, l ? "H" : "E");
+      return fail(b);
+    }
+  }
+  std::vector<std::vector<double>> data(nlists);
+  for (int l = 0; l < nlists; l++) {  // the whole file first: a truncated one changes nothing
+    data[l].resize(2 * (size_t)np[l] * (size_t)hd[1]);
+    if (!data[l].empty() && fread(data[l].data(), 8, data[l].size(), fp) != data[l].size())
+      return fail("dft file: read error (truncated file)");
+  }
+  for (int l = 0; l < nlists; l++)
+    if (dft_load(F, h, l, data[l].data(), (long long)(data[l].size() / 2), sign)) return -1;
   return 0;
 }
 

@@ -4752,6 +4752,111 @@ int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, in
   return rc();
 }
 
+// ------------------------------------------------- DFT data in list order
+// get / load / scale of the DFT values (save_dft_hdf5 / load_dft_hdf5 / dft_chunk::scale_dft,
+// src/dft.cpp:401-496).  The array is [slot/64][freq][slot%64]; the public order is the
+// reference's list order [list point][freq].  Gather and scatter walk the array in slot order:
+// one wave per block of 64 slots and tile of DFT_DT frequencies, so that every access to the
+// blocked array is one contiguous 1-KB span, and the 64 x DFT_DT tile is transposed through
+// LDS so that the list side moves DFT_DT * 16 B = one whole 128-B line per point.  inv[slot] is
+// the slot's index in the list, or -1 (another list, another rank's point, the padded tail).
+constexpr int DFT_DT = 8;      // frequencies per tile
+constexpr int DFT_DW = 4;      // waves (slot blocks) per workgroup
+constexpr int DFT_DP = 64 + 1; // LDS row pitch in double2
+
+__global__ void __launch_bounds__(64 * DFT_DW)
+    dft_gather_kernel(const double2 *__restrict__ dft, const int *__restrict__ inv,
+                      double2 *__restrict__ out, int nfreq, long long nblk) {
+  __shared__ double2 tile[DFT_DW][DFT_DT][DFT_DP];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long blk = (long long)blockIdx.x * DFT_DW + wv;
+  const int i0 = blockIdx.y * DFT_DT, ft = min(DFT_DT, nfreq - i0);
+  const bool on = blk < nblk;
+  const int k = on ? inv[blk * 64 + lane] : -1;
+  if (on) {
+    const double2 *__restrict__ dp = dft + (blk * nfreq + i0) * 64 + lane;
+#pragma unroll
+    for (int w = 0; w < DFT_DT; w++)
+      if (w < ft) tile[wv][w][lane] = dp[w * 64];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < DFT_DT; it++) {  // 8 lanes per point: its DFT_DT frequencies in a row
+    const int q = it * (64 / DFT_DT) + lane / DFT_DT, w = lane % DFT_DT;
+    const int kq = __shfl(k, q);
+    if (kq >= 0 && w < ft) out[(long long)kq * nfreq + i0 + w] = tile[wv][w][q];
+  }
+}
+
+// the inverse: dft[slot] = sign * in[list point] for the slots of this list
+__global__ void __launch_bounds__(64 * DFT_DW)
+    dft_scatter_kernel(double2 *__restrict__ dft, const int *__restrict__ inv,
+                       const double2 *__restrict__ in, double sign, int nfreq, long long nblk) {
+  __shared__ double2 tile[DFT_DW][DFT_DT][DFT_DP];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long blk = (long long)blockIdx.x * DFT_DW + wv;
+  const int i0 = blockIdx.y * DFT_DT, ft = min(DFT_DT, nfreq - i0);
+  const bool on = blk < nblk;
+  const int k = on ? inv[blk * 64 + lane] : -1;
+#pragma unroll
+  for (int it = 0; it < DFT_DT; it++) {
+    const int q = it * (64 / DFT_DT) + lane / DFT_DT, w = lane % DFT_DT;
+    const int kq = __shfl(k, q);
+    if (kq >= 0 && w < ft) {
+      const double2 v = in[(long long)kq * nfreq + i0 + w];
+      tile[wv][w][q] = make_double2(sign * v.x, sign * v.y);
+    }
+  }
+  __syncthreads();
+  if (k >= 0) {
+    double2 *__restrict__ dp = dft + (blk * nfreq + i0) * 64 + lane;
+#pragma unroll
+    for (int w = 0; w < DFT_DT; w++)
+      if (w < ft) dp[w * 64] = tile[wv][w][lane];
+  }
+}
+
+// dft[i] *= s with the two roundings per product of std::complex<double>::operator*= on finite
+// values (no contraction: -ffp-contract=off)
+__global__ void __launch_bounds__(256)
+    dft_scale_kernel(double2 *__restrict__ dft, double c, double d, long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double2 v = dft[i];
+    const double ac = v.x * c, bd = v.y * d, ad = v.x * d, bc = v.y * c;
+    dft[i] = make_double2(ac - bd, ad + bc);
+  }
+}
+
+int k_dft_gather(const double *dft, const int *inv, double *out, int nfreq, long long nslots,
+                 void *stream) {
+  const long long nblk = (nslots + 63) / 64;
+  if (nblk <= 0 || nfreq < 1) return 0;
+  const long long gx = (nblk + DFT_DW - 1) / DFT_DW, gy = (nfreq + DFT_DT - 1) / DFT_DT;
+  if (gx > 0x7fffffffLL || gy > 65535) return 2;
+  dft_gather_kernel<<<dim3((unsigned)gx, (unsigned)gy), 64 * DFT_DW, 0, (hipStream_t)stream>>>(
+      (const double2 *)dft, inv, (double2 *)out, nfreq, nblk);
+  return rc();
+}
+
+int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, int nfreq,
+                  long long nslots, void *stream) {
+  const long long nblk = (nslots + 63) / 64;
+  if (nblk <= 0 || nfreq < 1) return 0;
+  const long long gx = (nblk + DFT_DW - 1) / DFT_DW, gy = (nfreq + DFT_DT - 1) / DFT_DT;
+  if (gx > 0x7fffffffLL || gy > 65535) return 2;
+  dft_scatter_kernel<<<dim3((unsigned)gx, (unsigned)gy), 64 * DFT_DW, 0, (hipStream_t)stream>>>(
+      (double2 *)dft, inv, (const double2 *)in, sign, nfreq, nblk);
+  return rc();
+}
+
+int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream) {
+  if (ncomplex <= 0) return 0;
+  const long long nb = std::min<long long>((ncomplex + 255) / 256, 1 << 16);
+  dft_scale_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((double2 *)dft, re, im, ncomplex);
+  return rc();
+}
+
 // ------------------------------------------------- near-to-far-field transform
 // dft_near2far::farfield_lowlevel (src/near2far.cpp:340-387) for a block of NP far points and
 // a tile of FT frequencies over one workgroup's slot range.  Lanes are slots (the DFT array's

@@ -14,6 +14,7 @@ import numbers
 import os
 import time
 import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -326,6 +327,46 @@ class Source:
 # ---------------------------------------------------------------- flux monitors
 AUTOMATIC = -1
 
+# python/simulation.py:65-67: opaque containers of get_flux_data / get_near2far_data
+FluxData = namedtuple("FluxData", ["E", "H"])
+NearToFarData = namedtuple("NearToFarData", ["F"])
+
+
+class _DftData:
+    """What the DFT objects share: their accumulated values in list order.  The values are the
+    full lists on every rank (each point has one owner, so the sum over the ranks is exact):
+    data of a run on one GPU loads into a run on several, unlike the reference's "same number
+    of processors and chunk layout"."""
+
+    def _fields(self):
+        if self.handle is None or self.sim.fields is None:
+            raise RuntimeError("meep: the DFT object belongs to a simulation that was reset or "
+                               "never initialised")
+        return self.sim.fields
+
+    def _get(self, which):
+        f = self._fields()
+        d = f.dft_get(self.handle, which)
+        if f.nranks > 1:  # sum_to_all in pieces mnl_fields_allreduce can carry
+            v = d.view(np.float64)
+            for i in range(0, v.size, 1 << 20):
+                v[i:i + (1 << 20)] = f.sum_to_all(v[i:i + (1 << 20)])
+        return d
+
+    def _load(self, which, data, sign=1):
+        self._fields().dft_load(self.handle, which, data, sign)
+
+    def scale_dfts(self, s):
+        """dft_flux / dft_fields / dft_near2far ::scale_dfts (src/dft.cpp:573-576, 879;
+        src/near2far.cpp)"""
+        self._fields().dft_scale(self.handle, complex(s))
+
+    def save_hdf5(self, fname):
+        self._fields().dft_save(self.handle, fname)
+
+    def load_hdf5(self, fname, sign=1):
+        self._fields().dft_load_file(self.handle, fname, sign)
+
 
 def fix_dft_args(args, i):
     """(fcen, df, nfreq) -> frequency list (python/simulation.py:72-93)."""
@@ -372,7 +413,7 @@ def _normal_direction(dim, size):
     raise RuntimeError("Could not determine normal direction for given grid_volume.")
 
 
-class DftFlux:
+class DftFlux(_DftData):
     """python/simulation.py:687-760 (flux object); the DFT lives on the GPU."""
 
     def __init__(self, sim, freq, regions, decimation_factor):
@@ -402,7 +443,7 @@ class DftFlux:
         return list(self.sim.fields.flux(self.handle))
 
 
-class DftFields:
+class DftFields(_DftData):
     """python/simulation.py:793-810 (dft_fields object, created by add_dft_fields);
     the DFT lives on the GPU."""
 
@@ -443,7 +484,7 @@ def farfield_grid(lo, hi, resolution):
     return g, dims, dx
 
 
-class DftNear2Far:
+class DftNear2Far(_DftData):
     """python/simulation.py:811-905 (near2far object); the DFT lives on the GPU and the
     far-field transform runs there (fields.near2far_farfields)."""
 
@@ -524,6 +565,32 @@ def get_flux_freqs(f):
 def get_fluxes(f):
     """python/simulation.py:6022-6027"""
     return f.flux()
+
+
+def scale_flux_fields(s, flux):
+    """python/simulation.py:5997-6003: the Fourier-transformed fields of flux times the
+    complex s (load_minus_flux = load_flux, then s = -1)."""
+    flux.scale_dfts(s)
+
+
+def scale_near2far_fields(s, near2far):
+    """python/simulation.py:6058-6064"""
+    near2far.scale_dfts(s)
+
+
+def _data_to_str(d):  # python/simulation.py:5492-5497
+    if type(d) is complex:
+        sign = "+" if d.imag >= 0 else ""
+        return f"{d.real}{sign}{d.imag}i"
+    return str(d)
+
+
+def display_csv(sim, name, data):
+    """python/simulation.py:5463-5506: one "name<run_index>:, a, b, ..." line per row."""
+    for row in data:
+        row = row if isinstance(row, (list, tuple)) else [row]
+        if verbosity.meep > 0:
+            print("{}{}:, {}".format(name, sim.run_index, ", ".join(_data_to_str(v) for v in row)))
 
 
 # ---------------------------------------------------------------- step functions
@@ -1188,6 +1255,82 @@ class Simulation:
         self.dft_objects.append(flux)
         return flux
 
+    # -- the DFT data of a flux object (python/simulation.py:3548-3635).  Files are flat binary
+    # files (fields.dft_save), not HDF5; fname is used as given plus ".mnl".
+    def display_fluxes(self, *fluxes):
+        """The flux spectra as comma-separated "flux<run_index>:" lines (frequency, then
+        one column per flux object) when verbosity > 0."""
+        if verbosity.meep > 0:
+            display_csv(self, "flux", zip(get_flux_freqs(fluxes[0]),
+                                          *[get_fluxes(f) for f in fluxes]))
+
+    def get_flux_data(self, flux):
+        """The Fourier-transformed fields of flux as a FluxData of numpy arrays, to pass to
+        load_flux_data / load_minus_flux_data."""
+        return FluxData(E=flux._get(0), H=flux._get(1))
+
+    get_mode_data = get_flux_data
+
+    def load_flux_data(self, flux, fdata):
+        """Replace the Fourier-transformed fields of flux by fdata (of get_flux_data in a
+        simulation with the same cell and flux regions, on any number of GPUs)."""
+        self.init_sim()
+        flux._load(0, fdata.E)
+        flux._load(1, fdata.H)
+
+    load_mode_data = load_flux_data
+
+    def load_minus_flux_data(self, flux, fdata):
+        """load_flux_data, negated: the loaded fields are subtracted from what is accumulated
+        afterwards (one pass, instead of the reference's load and scale_dfts(-1))."""
+        self.init_sim()
+        flux._load(0, fdata.E, -1)
+        flux._load(1, fdata.H, -1)
+
+    load_minus_mode_data = load_minus_flux_data
+
+    def save_flux(self, fname, flux):
+        self.init_sim()
+        flux.save_hdf5(fname + ".mnl")
+
+    save_mode = save_flux
+
+    def load_flux(self, fname, flux):
+        self.init_sim()
+        flux.load_hdf5(fname + ".mnl")
+
+    load_mode = load_flux
+
+    def load_minus_flux(self, fname, flux):
+        self.init_sim()
+        flux.load_hdf5(fname + ".mnl", -1)
+
+    load_minus_mode = load_minus_flux
+
+    # -- and of a near2far object (python/simulation.py:3297-3355)
+    def get_near2far_data(self, near2far):
+        return NearToFarData(F=near2far._get(0))
+
+    def load_near2far_data(self, near2far, n2fdata):
+        self.init_sim()
+        near2far._load(0, n2fdata.F)
+
+    def load_minus_near2far_data(self, near2far, n2fdata):
+        self.init_sim()
+        near2far._load(0, n2fdata.F, -1)
+
+    def save_near2far(self, fname, near2far):
+        self.init_sim()
+        near2far.save_hdf5(fname + ".mnl")
+
+    def load_near2far(self, fname, near2far):
+        self.init_sim()
+        near2far.load_hdf5(fname + ".mnl")
+
+    def load_minus_near2far(self, fname, near2far):
+        self.init_sim()
+        near2far.load_hdf5(fname + ".mnl", -1)
+
     # -- near-to-far-field spectra (python/simulation.py:3073-3330)
     def add_near2far(self, *args, **kwargs):
         """add_near2far(fcen, df, nfreq, *Near2FarRegions, nperiods=1, decimation_factor=0) or
@@ -1391,6 +1534,8 @@ class Simulation:
     def reset_meep(self):
         """Simulation.reset_meep (python/simulation.py:4465-4477): drop fields, structure
         and DFT objects."""
+        for o in self.dft_objects:  # their handles belonged to the dropped fields
+            o.handle = None
         self.fields = None
         self.structure = None
         self.dft_objects = []
