@@ -383,18 +383,18 @@ int mnl_fields_set_temporal_blocking(mnl_fields *f, int on);
 /* Scheduling options of the fused step (no reference counterpart; an option only changes how
  * the same per-point arithmetic is scheduled, results are identical): which = 0 the narrow
  * x-face strip body of the temporal-blocking rim (MNL_TB_NARROW; the pair plan is rebuilt at
- * the next step), 1 DFT sampling plans with chi1inv as palette bytes (MNL_DFT_PAL; the plans
+ * the next step), 1 DFT sampling plans with chi1inv as palette bytes (the plans
  * are rebuilt at the next update), 2 / 3 / 4 the CUs the pair launches / the two-step launch /
- * the rim launches leave free (value = a count, -1 the default; MNL_TB_RES), 5 pairs sample DFT
+ * the rim launches leave free (value = a count, -1 the default), 5 pairs sample DFT
  * monitors from the two-step kernel's compact boxes (MNL_DFT_CMP; the pair plan is rebuilt),
  * 6 planes per rim item of a pair (value; 0 = the one-step chunk length), 7 the chi(2) NR box's
  * E phase beside the tile kernel (MNL_NR_EARLY), 8 planes per two-step item (value; 0 =
  * automatic; MNL_TB_ZCHUNK), 9 the most own columns of a two-step item (value 4..124; 0 = 124,
  * the widest the kernel's 128 columns of lanes hold), 11 pairs of steps with polarization chunks
- * (1, the default; MNL_TB_POL), 12 the first rim launch's items other than the narrow x-face
- * strips on a side stream beside the two-step kernel (1, the default; one rank; MNL_TB_R1A),
- * 16 a pair's step sources and NaN guard in one launch (1, the default; one rank;
- * MNL_TB_SRCGUARD).  For in-process A/B measurements (tools/ab_inproc.py).  10, 13, 14 and 15
+ * (1, the default), 12 the first rim launch's items other than the narrow x-face
+ * strips on a side stream beside the two-step kernel (1, the default; one rank),
+ * 16 a pair's step sources and NaN guard in one launch (1, the default; one rank).
+ * For in-process A/B measurements (tools/ab_inproc.py).  10, 13, 14 and 15
  * are retired (variants measured slower or no better and since removed):
  * they fail like any unknown number. */
 int mnl_fields_set_schedule(mnl_fields *f, int which, int value);

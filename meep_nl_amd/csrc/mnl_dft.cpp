@@ -206,6 +206,13 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
   for (auto &m : made) list.insert(list.begin(), m);
 }
 
+// updates per accumulation of a new monitor: DFT_KB, or MNL_DFT_BLOCK (1 .. DFT_KB), read when
+// the monitor is added
+static int dft_block() {
+  const char *e = getenv("MNL_DFT_BLOCK");
+  return e ? std::max(1, std::min(DFT_KB, atoi(e))) : DFT_KB;
+}
+
 // decimation_factor of fields::add_dft (src/dft.cpp:190-213)
 int dft_decimation(mnl_fields *F, const double *freqs, int nfreq, int decim) {
   if (decim != 0) return decim;
@@ -332,7 +339,7 @@ int dft_add_flux(mnl_fields *F, int nreg, const double *regions, const double *f
   for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]);
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
   for (int d = 0; d < 3; d++) o->wmin[d] = regions[d], o->wmax[d] = regions[3 + d];
-  if (const char *e = getenv("MNL_DFT_BLOCK")) o->kb = std::max(1, std::min(DFT_KB, atoi(e)));
+  o->kb = dft_block();
   const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
   std::vector<double> pwE, pwH;
   DftFluxH ho;  // H points collected separately, appended after the E points
@@ -369,7 +376,7 @@ int dft_add_fields(mnl_fields *F, int ncomp, const int *comps, const double wmin
   for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]);
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
   for (int d = 0; d < 3; d++) o->wmin[d] = wmin[d], o->wmax[d] = wmax[d];
-  if (const char *e = getenv("MNL_DFT_BLOCK")) o->kb = std::max(1, std::min(DFT_KB, atoi(e)));
+  o->kb = dft_block();
   const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
   std::vector<double> pwE, pwH;
   DftFluxH ho;
@@ -429,7 +436,7 @@ int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const doubl
   for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]), o->freq.push_back(freqs[i]);
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
   for (int d = 0; d < 3; d++) o->wmin[d] = regions[d], o->wmax[d] = regions[3 + d];
-  if (const char *e = getenv("MNL_DFT_BLOCK")) o->kb = std::max(1, std::min(DFT_KB, atoi(e)));
+  o->kb = dft_block();
   const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
   std::vector<double> pw, pwH;
   DftFluxH ho;

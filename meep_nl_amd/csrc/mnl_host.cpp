@@ -1383,15 +1383,15 @@ int tile_item_code(const mnl_fields *F, const FusedArgs &a, const Box &L, int x0
           zs - 1 >= L.lo[2] && ze <= L.hi[2];
   int body = 0;
   if (!*lean) {
-    const int lo[3] = {x0 - 1, y0, zs - 1}, hi[3] = {x0 + FX_HOST, y0 + 15, ze};
+    const int lo[3] = {x0 - 1, y0, zs - 1}, hi[3] = {x0 + FX, y0 + FR, ze};
     const int m = pml_dirs_in(F, lo, hi);
     body = m == 1 ? 1 : m == 2 ? 2 : m == 4 ? 3 : m == 0 ? 4 : m == 3 ? 6 : m == 5 ? 7 : 5;
   }
   int ownc = 0;
-  if (body >= 1 && body <= 3 && F->ownc) {
+  if (body >= 1 && body <= 3) {
     const int ylo = std::max(a.osh_lo[1], a.oun_lo[1]), yhi = std::min(a.osh_hi[1], a.oun_hi[1]);
     const int zlo = std::max(a.osh_lo[2], a.oun_lo[2]), zhi = std::min(a.osh_hi[2], a.oun_hi[2]);
-    ownc = (y0 >= ylo && y0 + 15 <= yhi && zs - 1 >= zlo && ze <= zhi && y0 + 15 <= g.N[1] - 1 &&
+    ownc = (y0 >= ylo && y0 + FR <= yhi && zs - 1 >= zlo && ze <= zhi && y0 + FR <= g.N[1] - 1 &&
             ze <= g.N[2] - 1) ? 1 : 0;
   }
   return (body << 24) | (ownc << 29);
@@ -1404,7 +1404,7 @@ int tile_item_code(const mnl_fields *F, const FusedArgs &a, const Box &L, int x0
 int strip_item_code(const mnl_fields *F, const FusedArgs &a, int x0, int x1, int y0, int y1, int zs,
                     int ze) {
   const DevGrid &g = F->g;
-  if (x1 - x0 + 1 > SW_HOST || (x0 & 15) || y1 - y0 > SOWN_HOST || y1 < y0 + 1 || ze <= zs)
+  if (x1 - x0 + 1 > SW_N || (x0 & 15) || y1 - y0 > SR_N - 1 || y1 < y0 + 1 || ze <= zs)
     return -1;
   const int lo[3] = {x0 - 1, y0, zs - 1}, hi[3] = {x1 + 1, y1 + 1, ze};
   if (pml_dirs_in(F, lo, hi) != 1) return -1;
@@ -1443,9 +1443,9 @@ bool make_fused_boxes(mnl_fields *F) {
   a.G = G;
   a.L = L;
   std::vector<int> xb, yb, zb, gyb;
-  split_range(xb, G.lo[0], G.hi[0] + 1, FX_HOST, 16);
+  split_range(xb, G.lo[0], G.hi[0] + 1, FX, 16);
   {
-    const int ny = G.hi[1] - G.lo[1] + 1, nt = (ny + 13) / 14;
+    const int ny = G.hi[1] - G.lo[1] + 1, nt = (ny + FOWN - 1) / FOWN;
     for (int t = 0; t < nt; t++) yb.push_back(G.lo[1] + (int)((long long)ny * t / nt));
   }
   int pzl = INT32_MAX, pzh = -1;
@@ -1466,7 +1466,7 @@ bool make_fused_boxes(mnl_fields *F) {
     if (F->nranks > 1 && zend - z0 > 2) cut.push_back(z0 + 2);
     // the lean box's z range: chunks from L.lo+1 to L.hi can run the lean body (their
     // halo planes lie in L), the ones outside hold the z-PML planes (short PML items)
-    if (F->tile_zcut && L.lo[2] <= L.hi[2]) {
+    if (L.lo[2] <= L.hi[2]) {
       if (L.lo[2] + 1 > z0 && L.lo[2] + 1 < zend) cut.push_back(L.lo[2] + 1);
       if (L.hi[2] > z0 && L.hi[2] < zend) cut.push_back(L.hi[2]);
     }
@@ -1559,7 +1559,7 @@ bool make_fused_boxes(mnl_fields *F) {
         for (int tx = 0; tx < a.nx; tx++) {
           const int y0 = a.gyb[ty] - 1;
           const int lo[3] = {a.xb[tx] - 1, y0, zs - 1};
-          const int hi[3] = {a.xb[tx] + FX_HOST, y0 + FUSED_GW_ROWS + 1, ze + 1};
+          const int hi[3] = {a.xb[tx] + FX, y0 + FUSED_GW_ROWS + 1, ze + 1};
           const int m = pml_dirs_in(F, lo, hi);
           const int v = tx | (ty << 8) | (ch << 16) |
                         (((m & ~2) == 0 ? 2 : (m & ~4) == 0 ? 4 : 7) << 24);
@@ -1579,7 +1579,6 @@ bool make_fused_boxes(mnl_fields *F) {
         const int code = tile_item_code(F, a, L, x0, x1, y0, y1, zs, ze, &in_l);
         const int body = (code >> 24) & 7;
         const int v = tx | (ty << 8) | (ch << 16) | code;
-        if (F->tile_body_mask >= 0 && !((F->tile_body_mask >> body) & 1)) continue;  // timing only
         if (F->nranks > 1 && ch == 0)
           early.push_back(v);
         else
@@ -1909,7 +1908,6 @@ struct EvPair {
 FusedArgs &fused_args(mnl_fields *F) {
   FusedArgs &fa = F->fgeo;
   const DevFields &f = F->f;
-  fa.blocks_per_cu = F->fused_bpc;
   fa.nelem = (long long)F->nlocal;
   fa.C = F->S.courant;
   fa.st1 = F->g.st[1];
@@ -1945,7 +1943,7 @@ FusedArgs &fused_args(mnl_fields *F) {
   fa.uidx = F->d_uidx;
   fa.utab = F->d_utab;
   fa.gflag = nullptr;
-  if (F->d_uidx && F->uniform) {
+  if (F->d_uidx) {
     // flags of the current tile / chunk geometry (rebuilt if make_fused_boxes changed it)
     unsigned long long sig = 1469598103934665603ULL;
     auto mix = [&](long long v) { sig = (sig ^ (unsigned long long)v) * 1099511628211ULL; };
@@ -2547,10 +2545,10 @@ int tb_plan(mnl_fields *F) {
       return 0;
     }
     std::vector<int> xs, zs;
-    split_range(xs, b.lo[0], b.hi[0] + 1, FX_HOST, 16);
+    split_range(xs, b.lo[0], b.hi[0] + 1, FX, 16);
     xs.push_back(b.hi[0] + 1);
     // a 16-column x-face box whose x-1 column is outside the grid or two-step: narrow strips
-    const bool narrow = F->tb_narrow && b.hi[0] - b.lo[0] + 1 == SW_HOST &&
+    const bool narrow = F->tb_narrow && b.hi[0] - b.lo[0] + 1 == SW_N &&
                         (b.lo[0] == 0 || col_two(b.lo[0] - 1, b.lo[1], b.hi[1], b.lo[2], b.hi[2]));
     std::vector<int> zcut = {b.lo[2], b.hi[2] + 1};
     // cuts at the lean box's z range (lean bodies for the planes inside it), unless a piece
@@ -2569,7 +2567,7 @@ int tb_plan(mnl_fields *F) {
     }
     zs.push_back(b.hi[2] + 1);
     if (narrow) {
-      const int ny = b.hi[1] - b.lo[1] + 1, nty = (ny + SOWN_HOST - 1) / SOWN_HOST;
+      const int ny = b.hi[1] - b.lo[1] + 1, nty = (ny + (SR_N - 1) - 1) / (SR_N - 1);
       std::vector<RI> items;
       bool ok = true;
       for (size_t iz = 0; iz + 1 < zs.size() && ok; iz++)
@@ -2594,13 +2592,13 @@ int tb_plan(mnl_fields *F) {
       if (ok) {
         for (const RI &it : items) {
           heavy.push_back(it);
-          F->rim_cells += double(SW_HOST) * (((it.g1 >> 16) - (it.g1 & 0xFFFF)) + 1) * it.planes;
+          F->rim_cells += double(SW_N) * (((it.g1 >> 16) - (it.g1 & 0xFFFF)) + 1) * it.planes;
         }
         F->tb_nnarrow += (int)items.size();
         continue;
       }
     }
-    const int ny = b.hi[1] - b.lo[1] + 1, nty = (ny + FOWN_HOST - 1) / FOWN_HOST;
+    const int ny = b.hi[1] - b.lo[1] + 1, nty = (ny + FOWN - 1) / FOWN;
     for (size_t iz = 0; iz + 1 < zs.size(); iz++)
       for (int ty = 0; ty < nty; ty++)
         for (size_t ix = 0; ix + 1 < xs.size(); ix++) {
@@ -2627,8 +2625,9 @@ int tb_plan(mnl_fields *F) {
   }
   // x-face strips of at most 32 columns (the rim left and right of L2) with the same rows,
   // planes and body (AX = 1) share one workgroup in pairs (pml_body<PAIR>): a narrow item
-  // costs about a whole tile's time per plane (one dependent round per plane)
-  if (!F->tb_nopair) {
+  // costs about a whole tile's time per plane (one dependent round per plane; unpaired strips
+  // measured 2.55 against 2.37 ms/step at 512^3, round 4)
+  {
     std::vector<RI> keep;
     std::vector<size_t> open;  // unpaired strips, by (rows, planes, code)
     for (const RI &it : heavy) {
@@ -3372,8 +3371,8 @@ int step_batch(mnl_fields *F, int nsteps) {
   size_t evi = 0;
   // timing events only (read after a stream synchronize): no system-scope fence when one is
   // recorded -- with it every record wrote back / invalidated the caches between the kernels,
-  // 0.4 % of a 512^3 step and 2.6 % of a 256^3 one (round 6; MNL_EV_FENCE=1 restores it)
-  const unsigned ev_flags = F->ev_fence ? hipEventDefault : hipEventDisableSystemFence;
+  // 0.4 % of a 512^3 step and 2.6 % of a 256^3 one (round 6)
+  const unsigned ev_flags = hipEventDisableSystemFence;
   // timing events of a phase on the main stream (or st)
   auto ev_begin = [&](int cat, hipStream_t st = nullptr) -> int {
     if (!F->profiling) return -1;
@@ -3953,22 +3952,13 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
     F->fused_zchunk = std::max(0, atoi(zc));
     F->fused_zchunk_env = true;  // the tuner keeps it
   }
-  if (const char *bp = getenv("MNL_FUSED_BPC")) F->fused_bpc = std::max(1, atoi(bp));
   if (const char *tb = getenv("MNL_TB")) F->tb_enabled = atoi(tb) != 0, F->tb_env = true;
   if (const char *tz = getenv("MNL_TB_ZCHUNK"))
     F->tb_zchunk = std::max(0, atoi(tz)), F->tb_zchunk_env = true;
   if (const char *tn = getenv("MNL_TB_NARROW")) F->tb_narrow = atoi(tn) != 0;
-  if (const char *tq = getenv("MNL_TB_POL")) F->tb_pol_on = atoi(tq) != 0;
-  if (const char *ta = getenv("MNL_TB_R1A")) F->tb_r1a = atoi(ta) != 0;
-  if (const char *ef = getenv("MNL_EV_FENCE")) F->ev_fence = atoi(ef) != 0;
-  if (const char *sg = getenv("MNL_TB_SRCGUARD")) F->tb_srcguard = atoi(sg) != 0;
   if (const char *to = getenv("MNL_TB_OOM")) F->tb_oom_test = atoi(to) != 0;
-  if (const char *dp = getenv("MNL_DFT_PAL")) F->dft_pal = atoi(dp) != 0;
   if (const char *dc = getenv("MNL_DFT_CMP")) F->dft_cmp = atoi(dc) != 0;
   if (const char *ne = getenv("MNL_NR_EARLY")) F->nr_early = atoi(ne) != 0;
-  if (const char *tr = getenv("MNL_TB_RES")) F->tb_res = std::max(0, atoi(tr));
-  if (const char *tp = getenv("MNL_TB_NOPAIR")) F->tb_nopair = atoi(tp) != 0;
-  if (const char *bm = getenv("MNL_TILE_BODY_MASK")) F->tile_body_mask = atoi(bm);
   if (const char *nf = getenv("MNL_NO_FUSED")) F->allow_fused = atoi(nf) == 0;
   if (const char *ne = getenv("MNL_NAN_EVERY")) F->nan_every = std::max(1, atoi(ne));
   if (const char *sg = getenv("MNL_STAGGER")) F->stagger = std::max(0, atoi(sg)) / 128 * 128;
@@ -3979,10 +3969,7 @@ mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, co
     const char *e = getenv(name);
     return e && e[0] == v;
   };
-  F->ownc = !env_is("MNL_NO_OWNC", '1');
-  F->tile_zcut = !env_is("MNL_ZCUT", '0');
   F->no_palette = env_is("MNL_NO_PALETTE", '1');
-  F->uniform = !env_is("MNL_UNIFORM", '0');
   if (const char *e = getenv("MNL_TILE_GEN_CUS")) {
     F->tile_gen_cus = std::max(0, atoi(e));
     F->tile_gen_cus_env = true;

@@ -28,11 +28,7 @@ using namespace mnl;
 typedef std::complex<double> cplx;
 
 namespace mnlh {
-constexpr int FX_HOST = 64;    // fused tile width (FX in mnl_kernels.hip)
-constexpr int FOWN_HOST = 14;  // own rows of a tile item (FOWN in mnl_kernels.hip)
 constexpr int TB_RES_CUS = 8;  // multi-rank: CUs left to the slab-face work (one per XCD)
-constexpr int SW_HOST = 16;     // narrow strip columns (SW_N in mnl_kernels.hip)
-constexpr int SOWN_HOST = 63;   // narrow strip own rows (SR_N - 1)
 constexpr int NAN_CH = 256;     // steps per chunk of a batch: the NaN flag is read after each
 
 constexpr double pi = 3.141592653589793238462643383276;  // meep::pi
@@ -309,13 +305,15 @@ struct mnl_fields {
   int *d_gitems = nullptr;
   size_t d_gitems_cap = 0;
   // one tile kernel over every chunk outside the polarization chunks (lean + PML bodies),
-  // the general kernel over those chunks only
-  bool tile_zcut = true;      // cut z chunks at the lean box's z range (short z-PML items)
-  int tile_body_mask = -1;   // MNL_TILE_BODY_MASK: step only these bodies (timing experiments)
+  // the general kernel over those chunks only; z chunks are cut at the lean box's z range
+  // (short z-PML items)
+  // Settled and no longer switchable (DESIGN.md sections 5, 24, 27): the OWNC item flag (AX = 1
+  // loop 475 -> 324 instructions per plane), per-item uniform palette words (3.094 -> 2.970
+  // ms/step), x-face rim strips paired two to a workgroup (2.55 -> 2.37 ms/step), one
+  // persistent workgroup per CU, timing events without the system fence (0.4 % of a 512^3
+  // step, 2.6 % of a 256^3 one).
   // diagnostic / A-B switches, read once when the fields are created (mnl_fields_create)
-  bool ownc = true;           // MNL_NO_OWNC=1: no OWNC item flag
   bool no_palette = false;    // MNL_NO_PALETTE=1: per-cell chi1inv loads, no byte palette
-  bool uniform = true;        // MNL_UNIFORM=0: per-cell palette loads in uniform items too
   bool tile_gen_cus_env = false;        // MNL_TILE_GEN_CUS given (the tuner keeps it)
   bool fused_zchunk_env = false;        // MNL_FUSED_ZCHUNK given (the tuner keeps it)
   bool tb_env = false, tb_zchunk_env = false;  // MNL_TB / MNL_TB_ZCHUNK given (the same)
@@ -345,7 +343,6 @@ struct mnl_fields {
   double *pp_E[3] = {nullptr, nullptr, nullptr}, *pp_H[3] = {nullptr, nullptr, nullptr};
   double *pp_UB[3] = {nullptr, nullptr, nullptr};
   int fused_zchunk = 0;
-  int fused_bpc = 1;
   bool fused_concurrent = false;  // last fused step ran the tile + general kernels concurrently
   int tile_gen_cus = 0;           // general kernel beside the tile kernel (CUs; 0: after it)
   unsigned long long *d_fused_ctr = nullptr;  // work-item counters of the fused kernels
@@ -383,12 +380,11 @@ struct mnl_fields {
   bool tb_enabled = true;           // MNL_TB=0 at creation: never
   int tb_zchunk = 0;                // planes per two-step item (0: automatic)
   int rim_zchunk = 0;               // planes per rim item of a pair (0: fused_zchunk)
-  bool tb_pol_on = true;            // MNL_TB_POL=0 / set_schedule 11: no pairs with them
-  bool tb_r1a = true;               // MNL_TB_R1A=0 / set_schedule 12: R1 after the two-step
+  bool tb_pol_on = true;            // set_schedule 11: no pairs with them
+  bool tb_r1a = true;               // set_schedule 12: R1 after the two-step
                                     // kernel instead of its non-strip items beside it
   int tb_rs0 = 0;                   // rim items before the narrow strips (one rank)
-  bool ev_fence = false;            // MNL_EV_FENCE=1: timing events with the default fence
-  bool tb_srcguard = true;          // MNL_TB_SRCGUARD=0 / set_schedule 16: a pair's sources
+  bool tb_srcguard = true;          // set_schedule 16: a pair's sources
                                     // and guard as two launches per step (default: one)
   bool tb_pol = false;              // the pairs step polarization chunks (general kernel, one
                                     // step at a time beside the rim launches; one rank)
@@ -406,15 +402,14 @@ struct mnl_fields {
   unsigned *d_tb_rflag = nullptr, *d_tb_uflag = nullptr;
   TB2Item *d_tb_items = nullptr;
   size_t tb_rcap = 0, tb_gcap = 0, tb_icap = 0;
-  bool tb_nopair = false;   // MNL_TB_NOPAIR=1: x-face rim strips one per workgroup (A/B)
   bool tb_last = false;     // the last batch of >= 2 steps stepped in pairs (tb_usable)
   int res_l = -1, res_r = -1;  // schedule options: the same for the two-step / rim launches only
-  int tb_res = -1;          // MNL_TB_RES: CUs the pairs' persistent launches leave free (-1:
+  int tb_res = -1;          // set_schedule 2: CUs the pairs' persistent launches leave free (-1:
                             // TB_RES_CUS with several ranks, 0 with one; A/B of the reservation)
   bool tb_oom = false;      // the middle buffer set did not fit: temporal blocking off
   bool tb_oom_test = false; // MNL_TB_OOM=1: its allocation fails (tests)
   bool tb_narrow = true;    // MNL_TB_NARROW=0: no narrow x-face strip items (A/B)
-  bool dft_pal = true;      // MNL_DFT_PAL=0: DFT sampling plans carry chi1inv as doubles (A/B)
+  bool dft_pal = true;      // set_schedule 1: DFT sampling plans carry chi1inv as palette bytes
   bool dft_cmp = true;      // MNL_DFT_CMP=0: pairs sample DFT monitors from the field arrays
   std::vector<TBCmp> tb_cmp;  // the compact DFT boxes of the current pair plan
   int tb_nnarrow = 0;       // narrow x-face strip items of the current plan

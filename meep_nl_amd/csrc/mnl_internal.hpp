@@ -242,18 +242,14 @@ constexpr int FUSED_MAXCH = 64;  // longest general chunk (planes)
 constexpr int FUSED_MAXGY = 256;
 // general items pack tx, ty, chunk in 8 bits each (mnl_kernels.hip, general_item)
 static_assert(FUSED_MAXZ <= 256 && FUSED_MAXX <= 256 && FUSED_MAXGY <= 256, "item encoding");
-#ifndef MNL_GW_ROWS
-#define MNL_GW_ROWS 10
-#endif
-#ifndef MNL_GEN_BPC
-#define MNL_GEN_BPC 1
-#endif
-constexpr int FUSED_GW_ROWS = MNL_GW_ROWS;  // general kernel: own rows per tile
-constexpr int FUSED_GEN_BPC = MNL_GEN_BPC;  // general kernel workgroups per CU
-#ifndef MNL_GEN_WPE
-#define MNL_GEN_WPE 1
-#endif
-constexpr int FUSED_GEN_WPE = MNL_GEN_WPE;  // general kernel: minimum waves per SIMD (VGPR cap)
+constexpr int FUSED_GW_ROWS = 10;  // general kernel: own rows per tile
+// Tile geometry of the tile kernel (mnl_kernels.hip), shared by the
+// kernels and the host's item lists
+constexpr int FX = 64;          // tile columns
+constexpr int FR = 15;          // rows per tile incl. the y-1 halo row
+constexpr int FOWN = FR - 1;    // own rows of a tile item
+constexpr int SW_N = 16;        // narrow strip (strip_body): columns
+constexpr int SR_N = 64;        // narrow strip: rows incl. the y-1 halo row
 struct FusedTab {                // per direction, indexed by global half-coordinate q
   const uint8_t *flag[3];        // PML chunk along the direction (f_u / W branches)
   const double *kms[3];          // kap - sig
@@ -283,7 +279,6 @@ struct FusedArgs {
   int N[3];           // local points per axis (array extents)
   int off[3];         // global index of local index 0 per axis
   int osh_lo[3], osh_hi[3], oun_lo[3], oun_hi[3];  // owned ranges within G per axis
-  int blocks_per_cu;  // persistent workgroups per CU (default 1)
   int wg_limit;       // > 0: at most this many persistent workgroups (CU split between
                       // the tile and general kernels running concurrently)
   long long nelem;    // elements per field array (selects 32-bit offsets)

@@ -23,24 +23,6 @@
 
 namespace mnl {
 
-// tile-kernel code-generation switches (variant builds for A/B timing; defaults are the
-// measured choices)
-#ifndef MNL_RS_AT
-#define MNL_RS_AT 1
-#endif
-#ifndef MNL_SKIP_B
-#define MNL_SKIP_B 1
-#endif
-#ifndef MNL_HOIST_X
-#define MNL_HOIST_X 0
-#endif
-#ifndef MNL_OWNC
-#define MNL_OWNC 1
-#endif
-#ifndef MNL_MULTI_DIST  // prefetch distance of the multi-axis PML bodies (AX = 3, 5, 7)
-#define MNL_MULTI_DIST 0
-#endif
-
 #define MNL_BX 64
 #define MNL_BY 4
 
@@ -1589,9 +1571,7 @@ int k_source(int ft, const DevGrid &g, const DevFields &f, const SrcDev &s, int 
 // the compiler's vmcnt accounting exact (in-order counter: a conditional store
 // would force a full drain at the join).
 // HBM traffic per cell: read B, D, u, write B, D (15 x 8 B).
-#define FX 64
-#define FR 15  // rows per tile incl. the y-1 halo row
-#define FOWN (FR - 1)
+// The tile geometry (FX, FR, FOWN, SW_N, SR_N) is in mnl_internal.hpp, shared with the host.
 
 typedef unsigned int mnl_u2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double ldg(const double *p, unsigned off) {
@@ -1621,35 +1601,13 @@ __device__ __forceinline__ unsigned ldu(gup p, unsigned off) {
   return *(gup)((const char __attribute__((address_space(1))) *)p + off);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const void *p, unsigned nrec) {
-  // null: zero records, every access out of range (loads 0, stores dropped)
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, p ? (int)nrec : 0,
-                                           0x00020000);
-}
 // descriptor of a scalar pointer built where it is used (the empty asm keeps the compiler
-// from hoisting it out of the loop); null: zero records, every access out of range
+// from hoisting it out of the loop); null: zero records, every access out of range (loads 0,
+// stores dropped)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc_at(unsigned long long v, unsigned nrec) {
   asm volatile("" : "+s"(v));
   return __builtin_amdgcn_make_buffer_rsrc((void *)v, 0, v ? (int)nrec : 0, 0x00020000);
 }
-// a PML-state array as pml_body holds it: a scalar pointer turned into a descriptor at each
-// use (R) or a descriptor built once
-template <bool R>
-struct RsArr {
-  __device__ static unsigned long long make(const void *p, unsigned) {
-    return (unsigned long long)sgpr_ptr(p);
-  }
-  __device__ static __amdgpu_buffer_rsrc_t get(unsigned long long v, unsigned nrec) {
-    return brsrc_at(v, nrec);
-  }
-};
-template <>
-struct RsArr<false> {
-  __device__ static __amdgpu_buffer_rsrc_t make(const void *p, unsigned nrec) {
-    return brsrc(p, nrec);
-  }
-  __device__ static __amdgpu_buffer_rsrc_t get(__amdgpu_buffer_rsrc_t r, unsigned) { return r; }
-};
 __device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
 }
@@ -1725,12 +1683,9 @@ typedef const FusedArgs __attribute__((address_space(4))) KFA;
 // The thread index behind an empty asm, per item: lane-derived offsets are then computed in
 // the body that uses them instead of being hoisted to the kernel entry as a union over all
 // bodies (kept in VGPRs across the item loop: scratch spills reloaded inside plane loops).
-#ifndef MNL_TID_OPQ
-#define MNL_TID_OPQ 1
-#endif
 __device__ __forceinline__ int tid_item() {
   int t = threadIdx.x;
-  if (MNL_TID_OPQ) asm volatile("" : "+v"(t));
+  asm volatile("" : "+v"(t));
   return t;
 }
 __device__ __forceinline__ KFA *kargs_opaque() {
@@ -1739,26 +1694,34 @@ __device__ __forceinline__ KFA *kargs_opaque() {
   return p;
 }
 
+// General tiles: items from the host-built list a.gitems (tx | ty << 8 | ch << 16 |
+// pml directions << 24): tiles of <= GEN_TX columns x FUSED_GW_ROWS rows (ty indexes a.gyb),
+// one row per wave plus the halo waves: 12 waves (168 VGPRs per lane).
+constexpr int GEN_TX = 64;
+constexpr int GEN_R = FUSED_GW_ROWS + 1;  // rows of a tile's footprint (row 0 = the y-1 halo row)
+constexpr int GEN_WAVES = GEN_R + (2 * GEN_R + 63) / 64;
+
 // General body over one item: any mix of PML chunks, walls, ghosts and owned
 // ranges (src/step_generic.cpp:69-253 and 576-906 per point; H and E by
 // update_eh, src/update_eh.cpp:67-363, with the W aux of PML chunks
 // represented by its value: W_H == B_old, W_E == chi1inv * D_old, which the
 // reference stores one step earlier).
-template <int UMODE, int TX, int R, int NW, int POL, int AX>
+template <int UMODE, int POL, int AX>
 __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
-                                              double (*sE)[R + 1][TX + 2],
-                                              double (*sB)[R][TX + 1], const double (*sU)[256],
+                                              double (*sE)[GEN_R + 1][GEN_TX + 2],
+                                              double (*sB)[GEN_R][GEN_TX + 1],
+                                              const double (*sU)[256],
                                               TabE (*sTx)[2], TabE (*sTy)[2], TabE (*sTz)[2],
                                               unsigned char (*sFx)[2], unsigned char (*sFy)[2],
                                               unsigned char (*sFz)[2]) {
-  // Tile: TX columns x R rows (row 0 = the y-1 halo row), own waves 0..NW-1 hold
-  // 64/TX rows each (lane -> column lane % TX); the waves after them hold the
-  // x-1 column (B recomputed), the E of the x+TX column and the corner.
+  // Tile: GEN_TX columns x GEN_R rows (row 0 = the y-1 halo row), own waves 0..GEN_R-1 hold
+  // one row each (lane -> column); the waves after them hold the x-1 column (B recomputed),
+  // the E of the x+GEN_TX column and the corner.
   constexpr bool HAS_U = UMODE != 0;
-  constexpr int RPW = 64 / TX, TPX = TX + 2, TPY = R + 1;
-  static_assert(NW * RPW == R, "rows");
+  constexpr int TPX = GEN_TX + 2, TPY = GEN_R + 1;
+  static_assert(GEN_TX == 64, "one row per wave");
   const int tid = tid_item(), lane = tid & 63, w = tid >> 6;
-  const bool hwave = __builtin_amdgcn_readfirstlane(w) >= NW - 1;
+  const bool hwave = __builtin_amdgcn_readfirstlane(w) >= GEN_R - 1;
   const double C = a.C;
   const unsigned s2 = (unsigned)(a.st2 * 8);
   const int x0 = it.x0, y0 = it.y0, zs = it.zs, ze = it.ze;
@@ -1799,22 +1762,23 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
   bool ownlike = false;
   int hrow = 0, hcol = 0, hc0 = 0, hdx = 0, hdy = 0;
   bool hslot = false;
-  if (w < NW) {
-    row = w * RPW + lane / TX;
-    ox = lane % TX;
+  if (w < GEN_R) {
+    row = w;
+    ox = lane;
     col = ox + 1;
     ownlike = true;
-    if (row == R - 1) {  // also loads E of the y+R row
-      hslot = true, hrow = R, hcol = col, hc0 = 0, hdx = ox, hdy = R;
+    if (row == GEN_R - 1) {  // also loads E of the y+GEN_R row
+      hslot = true, hrow = GEN_R, hcol = col, hc0 = 0, hdx = ox, hdy = GEN_R;
     }
   } else {
-    const int h = (w - NW) * 64 + lane;
-    if (h < R - 1) {  // x-1 column of own rows 1..R-1
+    const int h = (w - GEN_R) * 64 + lane;
+    if (h < GEN_R - 1) {  // x-1 column of own rows 1..GEN_R-1
       ownlike = true, row = h + 1, col = 0, ox = -1;
-    } else if (h < 2 * R - 1) {  // E of the x+TX column, rows 0..R-1
-      hslot = true, hrow = h - (R - 1), hcol = TX + 1, hc0 = 1, hdx = TX, hdy = hrow;
-    } else if (h == 2 * R - 1) {  // E(x0-1, y0+R)
-      hslot = true, hrow = R, hcol = 0, hc0 = 0, hdx = -1, hdy = R;
+    } else if (h < 2 * GEN_R - 1) {  // E of the x+GEN_TX column, rows 0..GEN_R-1
+      hslot = true, hrow = h - (GEN_R - 1), hcol = GEN_TX + 1, hc0 = 1, hdx = GEN_TX,
+      hdy = hrow;
+    } else if (h == 2 * GEN_R - 1) {  // E(x0-1, y0+GEN_R)
+      hslot = true, hrow = GEN_R, hcol = 0, hc0 = 0, hdx = -1, hdy = GEN_R;
     }
   }
   const int oy = row;
@@ -1831,7 +1795,7 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
                         (rng(gx, a.oun_lo[0], a.oun_hi[0]) ? 2u : 0u);
   const unsigned owny = (rng(gy, a.osh_lo[1], a.osh_hi[1]) ? 1u : 0u) |
                         (rng(gy, a.oun_lo[1], a.oun_hi[1]) ? 2u : 0u);
-  const bool stl = ownlike && w < NW && row >= 1 && gx >= x0 && gx <= it.x1 && gy <= it.y1;
+  const bool stl = ownlike && w < GEN_R && row >= 1 && gx >= x0 && gx <= it.x1 && gy <= it.y1;
   // halo slot point (E of comps hc0 and 2 at (hx, hy, k))
   const int hx = x0 + hdx, hy = y0 + hdy;
   const bool hA = hslot && hx >= 0 && hx < a.N[0] && hy >= 0 && hy < a.N[1] &&
@@ -2229,13 +2193,6 @@ __device__ __forceinline__ void fused_general(KFA &a, const ItemGeo &it,
   }
 }
 
-// General tiles: items from the host-built list a.gitems (tx | ty << 8 | ch << 16 |
-// pml directions << 24): tiles of <= GEN_TX columns x FUSED_GW_ROWS rows (ty indexes a.gyb),
-// one row per wave plus the halo waves: 12 waves (168 VGPRs per lane).
-constexpr int GEN_TX = 64;
-constexpr int GEN_R = FUSED_GW_ROWS + 1;  // rows of a tile's footprint (row 0 = the y-1 halo row)
-constexpr int GEN_WAVES = GEN_R + (2 * GEN_R + 63) / 64;
-
 struct GenLds {
   double sE[3][GEN_R + 1][GEN_TX + 2];
   double sB[3][GEN_R][GEN_TX + 1];
@@ -2255,12 +2212,13 @@ __device__ __forceinline__ void general_item(KFA &a, int item, unsigned uw, GenL
   itg.zs = a.zb[ch];
   itg.ze = a.zb[ch + 1];
   itg.uw = uw;
-  fused_general<UMODE, GEN_TX, GEN_R, GEN_R, POL, AX>(a, itg, L.sE, L.sB, sU, L.sTx, L.sTy, L.sTz,
-                                                      L.sFx, L.sFy, L.sFz);
+  fused_general<UMODE, POL, AX>(a, itg, L.sE, L.sB, sU, L.sTx, L.sTy, L.sTz, L.sFx, L.sFy,
+                                L.sFz);
 }
 
+// (second launch bound: one wave per SIMD, i.e. no VGPR cap tighter than the block size's)
 template <int UMODE, int POL>
-__global__ __launch_bounds__(64 * GEN_WAVES, FUSED_GEN_WPE) void fused_general_kernel(FusedArgs a) {
+__global__ __launch_bounds__(64 * GEN_WAVES, 1) void fused_general_kernel(FusedArgs a) {
   __shared__ double sU[UMODE == 2 ? 3 : 1][256];
   __shared__ GenLds L;
   __shared__ int s_item;
@@ -2297,7 +2255,7 @@ __global__ __launch_bounds__(64 * GEN_WAVES, FUSED_GEN_WPE) void fused_general_k
 // the lean box L: no PML, every component owned, H == B, E implicit.  1024 threads:
 // waves 0..FR-1 hold one row each (row 0 = the y-1 halo row, B recomputed), wave FR the
 // x-1 column (B recomputed), the E of the x+64 column and a corner.
-template <int UMODE, int DIST>
+template <int UMODE>
 __device__ __forceinline__ void lean_body(KFA &a, const ItemGeo &itg, unsigned uw,
                                           const double (*sU)[256], double (*sE)[FR + 1][FXL],
                                           double (*sB)[FR][FXL]) {
@@ -2305,7 +2263,6 @@ __device__ __forceinline__ void lean_body(KFA &a, const ItemGeo &itg, unsigned u
   const int tid = tid_item(), lane = tid & 63, w = tid >> 6;
   const int wu = __builtin_amdgcn_readfirstlane(w);  // wave-uniform
   const bool hwave = wu >= FR - 1;
-  constexpr bool SKIPB = MNL_SKIP_B;
   const int flo0 = a.L.lo[0], flo1 = a.L.lo[1], flo2 = a.L.lo[2];
   const int fhi0 = a.L.hi[0], fhi1 = a.L.hi[1], fhi2 = a.L.hi[2];
   const unsigned s2 = (unsigned)(a.st2 * 8);  // byte stride of one z plane
@@ -2420,9 +2377,9 @@ __device__ __forceinline__ void lean_body(KFA &a, const ItemGeo &itg, unsigned u
       }
       const unsigned ob = cbl + (unsigned)k * s2;
       // Bx of the x-1 column (wave FR) and By of the y-1 row (wave 0) feed no update: those
-      // lanes read one cached line instead of a line per row (MNL_SKIP_B)
-      q.b0 = ldg(Bv[0], (SKIPB && wu == FR) ? safe : ob);
-      q.b1 = ldg(Bv[1], (SKIPB && wu == 0) ? safe : ob);
+      // lanes read one cached line instead of a line per row
+      q.b0 = ldg(Bv[0], wu == FR ? safe : ob);
+      q.b1 = ldg(Bv[1], wu == 0 ? safe : ob);
       q.b2 = ldg(Bv[2], ob);
       q.hf = hF && zin(k);
       q.h0 = q.h1 = 0.0;
@@ -2465,6 +2422,7 @@ __device__ __forceinline__ void lean_body(KFA &a, const ItemGeo &itg, unsigned u
         ez *= ldg(Uv[2], o);
       }
     }
+    constexpr int DIST = 1;  // prefetch distance in planes
     FBatch q[DIST + 1];
 #pragma unroll
     for (int j = 0; j < DIST; j++) q[j] = load(min(zs - 1 + j, ze - 1));
@@ -2569,6 +2527,8 @@ __device__ __forceinline__ unsigned own_bits_of(int v, int sl, int sh, int ul, i
 // strips of temporal blocking) in one workgroup: lanes 0..31 the first (LDS columns 1..32, halo
 // columns 0 and 33), lanes 32..63 the second (it.xb0 .. it.xb1; LDS columns 35..66, halo 34 and
 // 67); the halo wave serves both.  Row and z logic are unchanged.
+// DIST: prefetch distance in planes, 1 for the face bodies and 0 for the multi-axis bodies
+// (AX = 3, 5, 7).
 template <int UMODE, int DIST, int AX, bool OWNC, bool PAIR = false>
 __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
                                          const double (*sU)[256], double (*sE)[FR + 1][FXL],
@@ -2578,8 +2538,6 @@ __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
   const int tid = tid_item(), lane = tid & 63, w = tid >> 6;
   const int wu = __builtin_amdgcn_readfirstlane(w);  // wave-uniform
   const bool hwave = wu >= FR - 1;
-  constexpr bool SKIPB = MNL_SKIP_B;
-  constexpr bool RSAT = MNL_RS_AT;
   const int x0 = it.x0, y0 = it.y0, zs = it.zs, ze = it.ze;
   const int zlo = zs - 1;  // z table position 0
   // ---- PML tables of the footprint -> LDS (x: x0-1 .. x0+64, y: y0 .. y0+FR,
@@ -2665,12 +2623,11 @@ __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
   const unsigned s2 = (unsigned)(a.st2 * 8);
   const double C = a.C;
   const unsigned nrec = (unsigned)min(a.nelem * 8, 0xFFFFFFFFLL);
-#define RSV(x) (RsArr<RSAT>::make((x), nrec))
-#define RS(p) (RsArr<RSAT>::get((p), nrec))
-  // PML-state arrays (null: every access out of range).  MNL_RS_AT (default): scalar
-  // pointers whose buffer descriptors are rebuilt at each use (RS): 4-SGPR descriptors of
-  // every array live across the z loop overflow the SGPRs and spill into VGPR lanes (a
-  // v_readlane per reload); MNL_RS_AT=0: descriptors built once before the loop
+#define RSV(x) ((unsigned long long)sgpr_ptr(x))
+#define RS(p) brsrc_at((p), nrec)
+  // PML-state arrays (null: every access out of range): scalar pointers (RSV) whose buffer
+  // descriptors are rebuilt at each use (RS): 4-SGPR descriptors of every array live across
+  // the z loop overflow the SGPRs and spill into VGPR lanes (a v_readlane per reload)
   const auto pBn0 = RSV(a.Bn[0]);
   const auto pBn1 = RSV(a.Bn[1]);
   const auto pBn2 = RSV(a.Bn[2]);
@@ -2717,23 +2674,10 @@ __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
   __syncthreads();  // tables visible
   // table accessors: direction d at this lane (x: column, y: row, z: plane position)
   const int px = col, py = row;
-  // MNL_HOIST_X: the x coefficients of a lane are the same on every plane; held in
-  // registers instead of re-read from LDS after every barrier
-  double tbx[3][2] = {{1, 1}, {1, 1}, {1, 1}};
-  bool hfx[2] = {false, false};
-  if (MNL_HOIST_X && PX) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) tbx[k][0] = P.v[0][k][0][px], tbx[k][1] = P.v[0][k][1][px];
-    hfx[0] = P.f[0][0][px] != 0, hfx[1] = P.f[0][1][px] != 0;
-  }
 #define T(d, coef, sft, pz) \
-  (((AX >> (d)) & 1) ? ((d) == 0 && MNL_HOIST_X ? tbx[coef][sft] \
-                                                : P.v[d][coef][sft][(d) == 0 ? px : ((d) == 1 ? py : (pz))]) \
-                     : 1.0)
+  (((AX >> (d)) & 1) ? P.v[d][coef][sft][(d) == 0 ? px : ((d) == 1 ? py : (pz))] : 1.0)
 #define F(d, sft, pz) \
-  (((AX >> (d)) & 1) ? ((d) == 0 && MNL_HOIST_X ? hfx[sft] \
-                                                : P.f[d][sft][(d) == 0 ? px : ((d) == 1 ? py : (pz))] != 0) \
-                     : false)
+  (((AX >> (d)) & 1) ? P.f[d][sft][(d) == 0 ? px : ((d) == 1 ? py : (pz))] != 0 : false)
   // W flags (PML chunk along the E component's own direction, shifted coordinate)
   const bool Wx = F(0, 1, 0), Wy = F(1, 1, 0);
 #define Wz(pz) F(2, 1, pz)
@@ -2769,8 +2713,8 @@ __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
     if (PY) QQ.es1 = bld(RS(pEo1), (o1 && Wy) ? o : MNL_OOB); \
     if (PZ) QQ.es2 = bld(RS(pEo2), (o2 && Wz(pz1)) ? o : MNL_OOB); \
     const unsigned ob = cbl + (unsigned)zc(KK) * s2; \
-    QQ.b0 = ldg(B0, (SKIPB && wu == FR) ? 0u : ob); /* unused: see lean_body */ \
-    QQ.b1 = ldg(B1, (SKIPB && wu == 0) ? 0u : ob); \
+    QQ.b0 = ldg(B0, wu == FR ? 0u : ob); /* unused: see lean_body */ \
+    QQ.b1 = ldg(B1, wu == 0 ? 0u : ob); \
     QQ.b2 = ldg(B2, ob); \
     QQ.h0 = QQ.h1 = 0.0; \
     QQ.hu0 = QQ.hu1 = 1.0; \
@@ -3011,13 +2955,12 @@ __device__ __forceinline__ void pml_body(KFA &a, const ItemGeo &it, unsigned uw,
 //     its own step n+2 values in the next set for R2).
 // AX = 1 (PML along x only) with every footprint point owned in y and z (OWNC): the update is
 // pml_body<AX = 1, OWNC>'s, operand for operand (src/step_generic.cpp:69-253, 576-906).
-constexpr int SW_N = 16, SR_N = 64, SXL = SW_N + 2;
+constexpr int SXL = SW_N + 2;
 template <int UMODE>
 __device__ __forceinline__ void strip_body(KFA &a, const ItemGeo &it, unsigned uw,
                                            const double (*sU)[256], double (*sE)[SR_N + 1][SXL],
                                            double (*sB)[SR_N][SXL], PTabL &P) {
   constexpr bool HAS_U = UMODE != 0;
-  constexpr bool RSAT = MNL_RS_AT;
   const int x0 = it.x0, x1 = it.x1, y0 = it.y0, y1 = it.y1, zs = it.zs, ze = it.ze;
   // ---- x PML tables of the footprint (positions 0 .. 17 = columns x0-1 .. x0+16) -> LDS
   for (int i = threadIdx.x; i < 2 * SXL; i += 1024) {
@@ -3058,8 +3001,8 @@ __device__ __forceinline__ void strip_body(KFA &a, const ItemGeo &it, unsigned u
   const unsigned s2 = (unsigned)(a.st2 * 8);
   const double C = a.C;
   const unsigned nrec = (unsigned)min(a.nelem * 8, 0xFFFFFFFFLL);
-#define RSV(x) (RsArr<RSAT>::make((x), nrec))
-#define RS(p) (RsArr<RSAT>::get((p), nrec))
+#define RSV(x) ((unsigned long long)sgpr_ptr(x))  // as in pml_body
+#define RS(p) brsrc_at((p), nrec)
   const auto pBn0 = RSV(a.Bn[0]);
   const auto pBn1 = RSV(a.Bn[1]);
   const auto pBn2 = RSV(a.Bn[2]);
@@ -3304,17 +3247,16 @@ constexpr int TILE_SE = 3 * (FR + 1) * FXL, TILE_SB = 3 * FR * FXL;
 constexpr int STRIP_SE = 3 * (SR_N + 1) * SXL, STRIP_SB = 3 * SR_N * SXL;
 constexpr int TILE_SM = TILE_SE + TILE_SB > STRIP_SE + STRIP_SB ? TILE_SE + TILE_SB
                                                                 : STRIP_SE + STRIP_SB;
-template <int UMODE, int DIST>
+template <int UMODE>
 __device__ __forceinline__ void tile_item_body(KFA &a, int item, const ItemGeo &itg,
                                                unsigned uw, const double (*sU)[256], double *sm,
                                                PTabL &sP) {
-  constexpr int MD = MNL_MULTI_DIST;
-  const bool ownc = MNL_OWNC && ((item >> 29) & 1);
+  const bool ownc = (item >> 29) & 1;
   double(*sE)[FR + 1][FXL] = reinterpret_cast<double(*)[FR + 1][FXL]>(sm);
   double(*sB)[FR][FXL] = reinterpret_cast<double(*)[FR][FXL]>(sm + TILE_SE);
   switch ((item >> 24) & 7) {
     case 0:
-      lean_body<UMODE, DIST>(a, itg, uw, sU, sE, sB);
+      lean_body<UMODE>(a, itg, uw, sU, sE, sB);
       break;
     case 1:
       if ((item >> 30) & 1) {  // narrow x-face strip (temporal-blocking rim; host: OWNC)
@@ -3322,38 +3264,38 @@ __device__ __forceinline__ void tile_item_body(KFA &a, int item, const ItemGeo &
                           reinterpret_cast<double(*)[SR_N][SXL]>(sm + STRIP_SE), sP);
       } else if (itg.xb0 >= 0) {  // paired x-face strips (temporal-blocking rim)
         if (ownc)
-          pml_body<UMODE, DIST, 1, true, true>(a, itg, uw, sU, sE, sB, sP);
+          pml_body<UMODE, 1, 1, true, true>(a, itg, uw, sU, sE, sB, sP);
         else
-          pml_body<UMODE, DIST, 1, false, true>(a, itg, uw, sU, sE, sB, sP);
+          pml_body<UMODE, 1, 1, false, true>(a, itg, uw, sU, sE, sB, sP);
       } else if (ownc) {
-        pml_body<UMODE, DIST, 1, true>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 1, true>(a, itg, uw, sU, sE, sB, sP);
       } else {
-        pml_body<UMODE, DIST, 1, false>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 1, false>(a, itg, uw, sU, sE, sB, sP);
       }
       break;
     case 2:
       if (ownc)
-        pml_body<UMODE, DIST, 2, true>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 2, true>(a, itg, uw, sU, sE, sB, sP);
       else
-        pml_body<UMODE, DIST, 2, false>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 2, false>(a, itg, uw, sU, sE, sB, sP);
       break;
     case 3:
       if (ownc)
-        pml_body<UMODE, DIST, 4, true>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 4, true>(a, itg, uw, sU, sE, sB, sP);
       else
-        pml_body<UMODE, DIST, 4, false>(a, itg, uw, sU, sE, sB, sP);
+        pml_body<UMODE, 1, 4, false>(a, itg, uw, sU, sE, sB, sP);
       break;
     case 4:
-      pml_body<UMODE, DIST, 0, false>(a, itg, uw, sU, sE, sB, sP);
+      pml_body<UMODE, 1, 0, false>(a, itg, uw, sU, sE, sB, sP);
       break;
     case 5:
-      pml_body<UMODE, MD, 7, false>(a, itg, uw, sU, sE, sB, sP);
+      pml_body<UMODE, 0, 7, false>(a, itg, uw, sU, sE, sB, sP);
       break;
     case 6:
-      pml_body<UMODE, MD, 3, false>(a, itg, uw, sU, sE, sB, sP);
+      pml_body<UMODE, 0, 3, false>(a, itg, uw, sU, sE, sB, sP);
       break;
     default:
-      pml_body<UMODE, MD, 5, false>(a, itg, uw, sU, sE, sB, sP);
+      pml_body<UMODE, 0, 5, false>(a, itg, uw, sU, sE, sB, sP);
       break;
   }
 }
@@ -3401,7 +3343,7 @@ __device__ __forceinline__ ItemGeo tile_item_geo(const FusedArgs &a, int item, i
   return itg;
 }
 
-template <int UMODE, int DIST, bool CLK>
+template <int UMODE, bool CLK>
 __global__ __launch_bounds__(1024) void fused_tile_kernel(FusedArgs a) {
   __shared__ double sU[UMODE == 2 ? 3 : 1][256];
   __shared__ double sm[TILE_SM];
@@ -3433,47 +3375,9 @@ __global__ __launch_bounds__(1024) void fused_tile_kernel(FusedArgs a) {
     __syncthreads();  // also separates LDS use of consecutive items
     const int item = s_item;
     if (item == -1) break;
-    tile_item_body<UMODE, DIST>(*kargs_opaque(), item, tile_item_geo(a, item, s_idx), s_uw, sU, sm,
-                                sP);
+    tile_item_body<UMODE>(*kargs_opaque(), item, tile_item_geo(a, item, s_idx), s_uw, sU, sm, sP);
   }
 }
-
-#ifdef MNL_ISA_PROBE
-// ISA inspection only (hipcc -DMNL_ISA_PROBE -S): one body per persistent kernel
-template <int UMODE, int BODY>
-__global__ __launch_bounds__(1024) void probe_kernel(FusedArgs a) {
-  __shared__ double sU[UMODE == 2 ? 3 : 1][256];
-  __shared__ double sm[TILE_SM];
-  __shared__ PTabL sP;
-  __shared__ int s_item;
-  unsigned long long *ctr = a.ctr + 16 * a.ctr_line;
-  for (;;) {
-    if (threadIdx.x == 0) {
-      const unsigned long long v = atomicAdd(ctr, 1ULL) - a.cbase;
-      s_item = v < (unsigned long long)(a.gend) ? a.titems[v] : -1;
-    }
-    __syncthreads();
-    const int item = s_item;
-    if (item == -1) break;
-    const ItemGeo itg = tile_item_geo(a, item, 0);
-    double(*sE)[FR + 1][FXL] = reinterpret_cast<double(*)[FR + 1][FXL]>(sm);
-    double(*sB)[FR][FXL] = reinterpret_cast<double(*)[FR][FXL]>(sm + TILE_SE);
-    if (BODY == 0)
-      strip_body<UMODE>(*kargs_opaque(), itg, ~0u, sU, reinterpret_cast<double(*)[SR_N + 1][SXL]>(sm),
-                        reinterpret_cast<double(*)[SR_N][SXL]>(sm + STRIP_SE), sP);
-    else if (BODY == 1)
-      pml_body<UMODE, 1, 1, true>(*kargs_opaque(), itg, ~0u, sU, sE, sB, sP);
-    else if (BODY == 2)
-      pml_body<UMODE, 1, 2, true>(*kargs_opaque(), itg, ~0u, sU, sE, sB, sP);
-    else
-      lean_body<UMODE, 1>(*kargs_opaque(), itg, ~0u, sU, sE, sB);
-  }
-}
-template __global__ void probe_kernel<2, 0>(FusedArgs);
-template __global__ void probe_kernel<2, 1>(FusedArgs);
-template __global__ void probe_kernel<2, 2>(FusedArgs);
-template __global__ void probe_kernel<2, 3>(FusedArgs);
-#endif
 
 // the tile kernel for palette mode um (2 palette, 1 f64 chi1inv, 0 none); the diagnostics
 // build when the item clock is on
@@ -3481,17 +3385,17 @@ void launch_tile(const FusedArgs &t, int um, dim3 grd, hipStream_t s) {
   const dim3 blk(1024);
   if (t.clk.rec) {
     if (um == 2)
-      fused_tile_kernel<2, 1, true><<<grd, blk, 0, s>>>(t);
+      fused_tile_kernel<2, true><<<grd, blk, 0, s>>>(t);
     else if (um == 1)
-      fused_tile_kernel<1, 1, true><<<grd, blk, 0, s>>>(t);
+      fused_tile_kernel<1, true><<<grd, blk, 0, s>>>(t);
     else
-      fused_tile_kernel<0, 1, true><<<grd, blk, 0, s>>>(t);
+      fused_tile_kernel<0, true><<<grd, blk, 0, s>>>(t);
   } else if (um == 2) {
-    fused_tile_kernel<2, 1, false><<<grd, blk, 0, s>>>(t);
+    fused_tile_kernel<2, false><<<grd, blk, 0, s>>>(t);
   } else if (um == 1) {
-    fused_tile_kernel<1, 1, false><<<grd, blk, 0, s>>>(t);
+    fused_tile_kernel<1, false><<<grd, blk, 0, s>>>(t);
   } else {
-    fused_tile_kernel<0, 1, false><<<grd, blk, 0, s>>>(t);
+    fused_tile_kernel<0, false><<<grd, blk, 0, s>>>(t);
   }
 }
 
@@ -3677,7 +3581,7 @@ int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bas
     if (which == 5) ie = a.ntit_e, line = 1;
     if (which == 6) ib = a.ntit_e, line = 2;
     if (ie <= ib) return 0;
-    long long nb = fused_grid_blocks(a.blocks_per_cu > 0 ? a.blocks_per_cu : 1);
+    long long nb = fused_grid_blocks(1);
     if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
     if (nb > ie - ib) nb = ie - ib;
     FusedArgs t = a;
@@ -3690,7 +3594,7 @@ int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bas
   int ib = 0, ie = a.ngen, line = 8;
   if (which == 2) ie = a.ngen_e, line = 10;
   if (which == 3) ib = a.ngen_e;
-  long long cus = fused_grid_blocks(FUSED_GEN_BPC);
+  long long cus = fused_grid_blocks(1);
   if (a.wg_limit > 0 && cus > a.wg_limit) cus = a.wg_limit;
   if (ie > ib) {
     FusedArgs g = a;
@@ -3708,7 +3612,7 @@ int k_tile_items(const FusedArgs &a, const int *items, const int *geo, const uns
   if (a.nelem * 8 >= (long long)MNL_OOB || !a.ctr || !items || !geo || line < 0 ||
       line >= FUSED_NCTR)
     return 2;
-  long long nb = fused_grid_blocks(a.blocks_per_cu > 0 ? a.blocks_per_cu : 1);
+  long long nb = fused_grid_blocks(1);
   if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
   if (nb > n) nb = n;
   FusedArgs t = a;

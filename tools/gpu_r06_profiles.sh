@@ -15,7 +15,7 @@ run3() {  # tag, env, args
 if want 512; then run3 r06p_512 "" "$H"; fi
 if want flux4; then run3 r06p_flux4 "" "$H --flux 4 --nfreq 50"; fi
 if want c2; then run3 r06p_c2 "" "--workload c2 --size 256 $H"; fi
-if want kerr; then run3 r06p_kerr_1s "MNL_TB_POL=0" "--workload kerr --size 256 $H"; fi
+if want kerr; then run3 r06p_kerr_1s "MNL_TB=0" "--workload kerr --size 256 $H"; fi
 if want kerrtb; then run3 r06p_kerr_tb "" "--workload kerr --size 256 $H"; fi
 if want kerrnr; then run3 r06p_kerr_nr "" "--workload kerr_nr --size 256 $H"; fi
 echo "profiles done"
