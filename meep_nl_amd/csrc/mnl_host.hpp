@@ -1,5 +1,6 @@
-// mnl_host.hpp -- the host side's shared internals (mnl_host.cpp: orchestration and the C-ABI,
-// mnl_dft.cpp: DFT monitors): source times, the structure and fields objects, allocation.
+// mnl_host.hpp -- the host side's shared internals: source times, the structure and fields
+// objects, allocation, buffer sets, phase timing, and what each host source file (mnl_host.cpp
+// lists them) offers the others.
 // Internal to libmnl.so (not installed; the API is include/meep_nl_amd.h).
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -30,6 +31,18 @@ typedef std::complex<double> cplx;
 namespace mnlh {
 constexpr int TB_RES_CUS = 8;  // multi-rank: CUs left to the slab-face work (one per XCD)
 constexpr int NAN_CH = 256;     // steps per chunk of a batch: the NaN flag is read after each
+
+// phase timers (mnl_fields::timer_ms / timer_count, filled by PhaseTimer)
+enum {
+  TM_B = 0, TM_H, TM_D, TM_E, TM_SRC, TM_HALO, TM_BINT, TM_DINT, TM_GEN, TM_DFT, TM_DFTF,
+  TM_TB,   // two-step kernel (temporal blocking), one launch per pair of steps
+  TM_RIM,  // rim launches of the pairs (two per pair)
+  TM_CHAIN,  // multi-rank pairs: a slab-face chain on the comm stream (two per pair)
+  TM_WAIT,   // multi-rank pairs: the main stream waiting for the chain's E ghost (two per pair)
+  TM_N
+};
+constexpr int TM_CAP = 16;  // length of timer_ms / timer_count
+static_assert(TM_N <= TM_CAP, "a phase timer without a slot");
 
 constexpr double pi = 3.141592653589793238462643383276;  // meep::pi
 extern thread_local std::string g_err;
@@ -248,23 +261,13 @@ struct DftFluxH {
   double *d_list = nullptr;
   size_t list_cap = 0;                // doubles
   ~DftFluxH() {
-    if (d_inv[0]) (void)hipFree(d_inv[0]);
-    if (d_inv[1]) (void)hipFree(d_inv[1]);
-    if (d_list) (void)hipFree(d_list);
-    if (d_n2f_part) (void)hipFree(d_n2f_part);
-    if (d_n2f_xyz) (void)hipFree(d_n2f_xyz);
-    if (d_n2f_out) (void)hipFree(d_n2f_out);
-    if (d_ph) (void)hipFree(d_ph);
-    if (d_sidx) (void)hipFree(d_sidx);
-    if (d_ssel) (void)hipFree(d_ssel);
-    if (d_spal) (void)hipFree(d_spal);
-    if (d_su) (void)hipFree(d_su);
-    if (d_bad) (void)hipFree(d_bad);
-    if (d_cmp) (void)hipFree(d_cmp);
-    if (d_sci) (void)hipFree(d_sci);
+    for (void *p : {(void *)d_inv[0], (void *)d_inv[1], (void *)d_list, (void *)d_n2f_part,
+                    (void *)d_n2f_xyz, (void *)d_n2f_out, (void *)d_ph, (void *)d_sidx,
+                    (void *)d_ssel, (void *)d_spal, d_su, (void *)d_bad, (void *)d_cmp,
+                    (void *)d_sci})
+      if (p) (void)hipFree(p);
   }
 };
-
 
 // =============================================================== fields
 struct mnl_fields {
@@ -459,8 +462,8 @@ struct mnl_fields {
   double sink_s[MNL_NUM_TIME_SINKS] = {0};
   double last_out_wall = -1;  // "on time step" output (src/step.cpp:44-56)
   long long last_out_t = 0;
-  double timer_ms[16] = {0};
-  long long timer_count[16] = {0};
+  double timer_ms[TM_CAP] = {0};
+  long long timer_count[TM_CAP] = {0};
   double n2f_ms[2] = {0, 0};         // near2far: far-field kernel, reduce kernel (HIP events)
   long long n2f_count[2] = {0, 0};
   double dftio_ms[3] = {0, 0, 0};    // DFT data: gather, scatter, scale kernels (HIP events)
@@ -498,12 +501,102 @@ struct mnl_fields {
 
 namespace mnlh {
 
-bool in_fused_box(const mnl_fields *F, int c, const int jg[3]);
-int nan_launch(mnl_fields *F, hipStream_t st = nullptr, double *const *E = nullptr,
-               double *const *D = nullptr);
-void nan_count(mnl_fields *F, int k);
-int nan_result(mnl_fields *F);
-int nan_terms_build(mnl_fields *F);
+// ---- buffer sets
+// one buffer set of the fused step's per-point state (B, D, stored E, separate H, f_u of B):
+// the current arrays, their ping-pong partners, the pairs' middle set.  A partner is null
+// where the current array is null.
+struct Set5 {
+  double *B[3], *D[3], *E[3], *H[3], *UB[3];
+};
+inline Set5 set_cur(const mnl_fields *F) {
+  Set5 s;
+  for (int d = 0; d < 3; d++)
+    s.B[d] = F->f.B[d], s.D[d] = F->f.D[d], s.E[d] = F->f.E[d], s.H[d] = F->f.H[d],
+    s.UB[d] = F->f.UB[d];
+  return s;
+}
+inline Set5 set_nxt(const mnl_fields *F) {
+  Set5 s;
+  for (int d = 0; d < 3; d++)
+    s.B[d] = F->f.Bn[d], s.D[d] = F->f.Dn[d], s.E[d] = F->f.E[d] ? F->f.En[d] : nullptr,
+    s.H[d] = F->f.H[d] ? F->f.Hn[d] : nullptr, s.UB[d] = F->f.UB[d] ? F->f.UBn[d] : nullptr;
+  return s;
+}
+inline Set5 set_mid(const mnl_fields *F) {
+  Set5 s;
+  for (int d = 0; d < 3; d++)
+    s.B[d] = F->pp3_B[d], s.D[d] = F->pp3_D[d], s.E[d] = F->f.E[d] ? F->pp3_E[d] : nullptr,
+    s.H[d] = F->f.H[d] ? F->pp3_H[d] : nullptr, s.UB[d] = F->f.UB[d] ? F->pp3_UB[d] : nullptr;
+  return s;
+}
+// fused-kernel arguments of one step from set `o` to set `n`
+inline void args_sets(FusedArgs &a, const Set5 &o, const Set5 &n) {
+  for (int d = 0; d < 3; d++) {
+    a.Bo[d] = o.B[d], a.Do[d] = o.D[d], a.E[d] = o.E[d], a.Ho[d] = o.H[d], a.UBo[d] = o.UB[d];
+    a.Bn[d] = n.B[d], a.Dn[d] = n.D[d], a.En[d] = n.E[d], a.Hn[d] = n.H[d], a.UBn[d] = n.UB[d];
+  }
+}
+// `f` with set `o` as its current arrays (exchanges, shell kernels and DFT updates read a
+// DevFields' pointers when enqueued) ...
+inline DevFields fields_at(DevFields f, const Set5 &o) {
+  for (int d = 0; d < 3; d++)
+    f.B[d] = o.B[d], f.D[d] = o.D[d], f.E[d] = o.E[d], f.H[d] = o.H[d], f.UB[d] = o.UB[d];
+  return f;
+}
+// ... and set `n` as their ping-pong partners
+inline DevFields fields_at(DevFields f, const Set5 &o, const Set5 &n) {
+  f = fields_at(f, o);
+  for (int d = 0; d < 3; d++) {
+    f.Bn[d] = n.B[d], f.Dn[d] = n.D[d], f.En[d] = o.E[d] ? n.E[d] : nullptr;
+    f.Hn[d] = o.H[d] ? n.H[d] : nullptr, f.UBn[d] = o.UB[d] ? n.UB[d] : nullptr;
+  }
+  return f;
+}
+// the ping-pong swap after a fused step
+inline void swap_cur_nxt(DevFields &f) {
+  for (int d = 0; d < 3; d++) {
+    std::swap(f.B[d], f.Bn[d]);
+    std::swap(f.D[d], f.Dn[d]);
+    std::swap(f.E[d], f.En[d]);
+    std::swap(f.H[d], f.Hn[d]);
+    std::swap(f.UB[d], f.UBn[d]);
+  }
+}
+
+// ---- phase timing
+// The timing events of a batch's phases; flush() adds their times to timer_ms / timer_count at
+// the end of a chunk.  The events are read only after a stream synchronize, so they carry no
+// system-scope fence when recorded -- with it every record wrote back / invalidated the caches
+// between the kernels, 0.4 % of a 512^3 step and 2.6 % of a 256^3 one (round 6).
+struct PhaseTimer {
+  explicit PhaseTimer(mnl_fields *fields) : F(fields) {}
+  int begin(int cat, hipStream_t st = nullptr);  // on the main stream (or st); -1: profiling off
+  void end(int k, hipStream_t st = nullptr);
+  // a phase that starts where phase k ended: its start is k's end event (one record fewer
+  // between two back-to-back kernels)
+  int next(int k, int cat);
+  int flush();
+
+ private:
+  struct Span { hipEvent_t a, b; int cat; };
+  bool reserve_events();  // the pool holds two events for the next span
+  mnl_fields *F;
+  std::vector<Span> spans;
+};
+
+// a host list on the device: the buffer grows as needed, the copy is enqueued on the main stream
+template <class T>
+int dev_upload(mnl_fields *F, T **d, size_t &cap, const std::vector<T> &h) {
+  if (h.empty()) return 0;
+  if (cap < h.size()) {
+    if (*d) (void)hipFree(*d);
+    *d = nullptr;
+    HIPCHK(hipMalloc(d, h.size() * sizeof(T)));
+    cap = h.size();
+  }
+  HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, F->stream));
+  return 0;
+}
 
 // Field-sized arrays start at staggered offsets (a multiple of 128 B, different
 // for every array) so that the many streams one fused step reads and writes at
@@ -558,13 +651,76 @@ int dev_alloc(mnl_fields *F, T **p, size_t n, bool zero = true) {
   return 0;
 }
 
-// ---- mnl_host.cpp, used by mnl_dft.cpp
+inline int check_comp(int c) {
+  if (c < 0 || c >= MNL_NUM_COMPONENTS) return fail("invalid component");
+  return 0;
+}
+inline bool all_eq(const std::vector<double> &v, double x) {
+  for (double y : v)
+    if (y != x) return false;
+  return true;
+}
+
+// ---- mnl_setup.cpp: PML tables, grid, allocation, materials
 struct ZoneIv {
   int c0, c1, zone;  // chunk covers half-coords [c0, c1] relative to io
 };
 std::vector<ZoneIv> zone_intervals(const mnl_structure &S, int d);
+void slab_range(int ncell, int rank, int nranks, int *lo, int *hi);
+bool has_field(const mnl_structure &S, int c);
+int require_component(mnl_fields *F, int c);
+int finalize_fields(mnl_fields *F);
+int initialize_field(mnl_fields *F, int c, const double *host);
+
+// ---- mnl_sources.cpp: sources, local indices, get_field
 int build_source_lists(mnl_fields *F);
+SrcDev src_dev(mnl_fields *F, int t, const double *J);
 void interpolate(const mnl_structure &S, int c, const double pc[3], int locs[8][3], double w[8]);
+long long local_index(const mnl_fields *F, int c, const int jg[3], bool include_wall);
+int get_field(mnl_fields *F, int c, const double pos[3], double *out, bool reduce);
+int add_source_any(mnl_fields *F, int comp, int kind, const double *p, int np, mnl_src_func func,
+                   void *fdata, const double vmin[3], const double vmax[3], double amp_re,
+                   double amp_im, int is_integrated, mnl_amp_func afunc, void *adata);
+
+// ---- mnl_fused.cpp: planning of the fused step
+void split_range(std::vector<int> &b, int lo, int hi_excl, int step, int align);
+int tile_item_code(const mnl_fields *F, const FusedArgs &a, const Box &L, int x0, int x1, int y0,
+                   int y1, int zs, int ze, bool *lean);
+int strip_item_code(const mnl_fields *F, const FusedArgs &a, int x0, int x1, int y0, int y1, int zs,
+                    int ze);
+bool in_fused_box(const mnl_fields *F, int c, const int jg[3]);
+bool fused_agreed(mnl_fields *F);
+int set_fused(mnl_fields *F, bool on);
+FusedArgs &fused_args(mnl_fields *F);
+
+// ---- mnl_tb.cpp: pairs of steps (temporal blocking)
+int tb_usable(mnl_fields *F, bool *ok);
+int tb_pair(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, PhaseTimer &pt, long long t_mid);
+int tb_pair_multi(mnl_fields *F, const SrcDev &s0, const SrcDev &s1, PhaseTimer &pt,
+                  long long t_mid);
+int tb_chain_join(mnl_fields *F);
+
+// ---- mnl_step.cpp: the step path and the NaN guard
+constexpr int NR_HARD_CAP = 4096;  // deferred NR problems per E update (more: solved in place)
+int exchange(mnl_fields *F, int kind, hipStream_t st = nullptr);
+int h_lazy_copy(mnl_fields *F);
+int u_lazy_copy(mnl_fields *F, int which);
+int e_lazy_copy(mnl_fields *F);
+int update_h_any(mnl_fields *F, const BoxList &sl, bool pols);
+int nr_split(mnl_fields *F);
+int nr_defer_begin(mnl_fields *F, hipStream_t st = nullptr);
+int nr_defer_end(mnl_fields *F, hipStream_t st = nullptr);
+int fused_fail(const char *what, int kr);
+int ensure_aux_stream(mnl_fields *F);
+int shell_step(mnl_fields *F, hipStream_t st, bool fuseE, const SrcDev &sD,
+               hipEvent_t h_in = nullptr);
+int nan_launch(mnl_fields *F, hipStream_t st = nullptr, double *const *E = nullptr,
+               double *const *D = nullptr);
+void nan_count(mnl_fields *F, int k);
+int fields_step(mnl_fields *F, int nsteps);
+
+// ---- mnl_tune.cpp
+int tune(mnl_fields *F, int reps, int *zchunk, int *gen_cus);
 
 // ---- mnl_dft.cpp: loop_in_chunks helpers and DFT monitors
 inline int my_round(double x) { return int(floor(fabs(x) + 0.5) * (x < 0 ? -1 : 1)); }
@@ -596,8 +752,6 @@ int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const doubl
                      int decimation, int nperiods);
 int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out);
 int n2f_points(mnl_fields *F, int h, double *out, long long npoints);
-// ---- mnl_host.cpp, used by mnl_dft.cpp
-int timed_allreduce(mnl_fields *F, double *v, int n);
 
 // ---- mnl_io.cpp: checkpoints, array slices, field energy
 struct CkEntry {
@@ -622,13 +776,6 @@ int array_slice(mnl_fields *F, int c, const double vmin[3], const double vmax[3]
                 int *rank, long long dims[3], double *out, long long nout);
 int energy_in_box(mnl_fields *F, int which, const double wmin[3], const double wmax[3],
                   double *out);
-// ---- mnl_host.cpp, used by mnl_io.cpp
-int exchange(mnl_fields *F, int kind, hipStream_t st = nullptr);
-int h_lazy_copy(mnl_fields *F);
-int u_lazy_copy(mnl_fields *F, int which);
-bool has_field(const mnl_structure &S, int c);
-int set_fused(mnl_fields *F, bool on);
-SrcDev src_dev(mnl_fields *F, int t, const double *J);
-int update_h_any(mnl_fields *F, const BoxList &sl, bool pols);
+int timed_allreduce(mnl_fields *F, double *v, int n);
 
 }  // namespace mnlh
