@@ -342,61 +342,100 @@ int mnl_fields_traffic_model(mnl_fields *f, double *bytes_per_cell_step, double 
  * (used automatically for 3-D non-dispersive, non-NR configurations without
  * magnetic or integrated sources).  Results are identical either way. */
 int mnl_fields_set_fused(mnl_fields *f, int allow);
-/* bit 0: the last step ran the fused interior kernel; bit 1: it read chi1inv
- * through the palette (DESIGN.md "chi1inv palette"); bit 2: field arrays are
- * requested physically contiguous; bit 4: the fused step ran as the single tile
- * kernel (lean + PML bodies), which is the only fused step there
- * is: set whenever bit 0 is; bits 8-15: how many
- * contiguity requests the driver could not satisfy (plain allocations instead). */
+/* How the last step ran and how the fields are allocated: *fused = an OR of these bits. */
+enum {
+  MNL_MODE_FUSED = 1,       /* the last step ran the fused interior kernel */
+  MNL_MODE_PALETTE = 2,     /* it read chi1inv through the palette (DESIGN.md "chi1inv palette") */
+  MNL_MODE_CONTIG = 4,      /* field arrays are requested physically contiguous (MNL_CONTIG) */
+  MNL_MODE_TILE = 16,       /* it ran as the single tile kernel (lean + PML bodies, DESIGN.md
+                               section 5), the only fused step there is: set whenever FUSED is */
+  MNL_MODE_CONCURRENT = 32, /* the polarization chunks' general kernel ran beside the tile kernel
+                               on a CU split: MNL_KSTAT_TILE then spans both launches */
+  MNL_MODE_FALLBACKS_SHIFT = 8 /* bits 8-15: contiguity requests the driver could not satisfy
+                                  (plain allocations instead), at most 255 */
+};
 int mnl_fields_mode(mnl_fields *f, int *fused);
 /* Enable HIP-event timing around every sub-step kernel group (on the stream
  * the kernels run on) and reset the accumulated timers. */
 int mnl_fields_set_profiling(mnl_fields *f, int on);
-/* Accumulated launches / total ms of the dominant interior kernel since the
- * last mnl_fields_set_profiling, and its algorithmic bytes per launch.
- * which = 0: the tile kernel (fused mode) or curl B = step_db(B_stuff);
- * which = 1: curl D = step_db(D_stuff) (unfused mode);
- * which = 2: general fused kernel (the polarization chunks);
- * which = 3: the DFT updates of one step (all flux objects);
- * which = 4: the E update (update_eh(E_stuff): chi(2) Newton-Raphson,
- *            Lorentzian P), unfused mode; bytes 0 (not HBM-bound);
- * which = 5: temporal blocking: launches = pairs of
- *            steps, total_ms = every launch of the pairs, bytes per pair;
- * which = 6: rim launches that run alone (one step each);
- * which = 11, 12, 13: the gather, scatter and scale kernels of the DFT data calls
- *            (mnl_fields_dft_get / _load / _scale), always timed; bytes of the last launch. */
+/* Accumulated launches / total ms of one kernel group since the last
+ * mnl_fields_set_profiling, and its algorithmic bytes per launch (0 where the group is not
+ * HBM-bound or has no model).  which = one of: */
+enum {
+  MNL_KSTAT_TILE = 0,       /* the tile kernel (fused mode) or curl B = step_db(B_stuff) */
+  MNL_KSTAT_CURL_D = 1,     /* curl D = step_db(D_stuff) (unfused mode) */
+  MNL_KSTAT_GENERAL = 2,    /* the general fused kernel (the polarization chunks) */
+  MNL_KSTAT_DFT = 3,        /* the DFT updates of one step (all DFT objects) */
+  MNL_KSTAT_E_UPDATE = 4,   /* update_eh(E_stuff): chi(2) Newton-Raphson, Lorentzian P; unfused */
+  MNL_KSTAT_PAIRS = 5,      /* temporal blocking: launches = pairs of
+                               steps, total_ms = every launch of the pairs, bytes per pair */
+  MNL_KSTAT_RIM = 6,        /* the rim launches of the pairs, one step each */
+  MNL_KSTAT_CHAIN = 7,      /* multi-rank pairs: the slab-face chains on the comm stream */
+  MNL_KSTAT_GHOST_WAIT = 8, /* multi-rank pairs: the main stream waiting for a chain's E ghost */
+  MNL_KSTAT_N2F_FAR = 9,    /* near2far: the far-field kernel (mnl_fields_near2far_farfields) */
+  MNL_KSTAT_N2F_REDUCE = 10, /* near2far: the reduce kernel of the far-field transform */
+  /* the kernels of the DFT data calls: always timed, bytes of the last launch */
+  MNL_KSTAT_DFT_GET = 11,   /* the gather kernel of mnl_fields_dft_get */
+  MNL_KSTAT_DFT_LOAD = 12,  /* the scatter kernel of mnl_fields_dft_load */
+  MNL_KSTAT_DFT_SCALE = 13, /* the scale kernel of mnl_fields_dft_scale */
+  MNL_NUM_KSTATS = 14
+};
 int mnl_fields_kernel_stats(mnl_fields *f, int which, long long *launches, double *total_ms,
                             double *bytes_per_launch);
 /* Temporal blocking (no reference counterpart: how this build steps pairs of
- * fields::step(), src/step.cpp:35-140).  out[0..n) of:
- * active (1: the current fused geometry steps pairs), own cells of the two-step
- * items, border points (upper bound), own cells of mixed-palette two-step items,
- * rim cells, mixed-palette rim cells, two-step items, rim items, planes of the
- * first two-step item (the longest), narrow x-face strip items among the rim items,
- * enabled (pairs allowed: set_temporal_blocking / MNL_TB / the tuner), the two-step chunk
- * setting (0: automatic), the most own columns of a two-step item (124 unless set or tuned),
- * polarization chunks stepped inside the pairs (1). */
+ * fields::step(), src/step.cpp:35-140): the first n of these slots
+ * of the current fused geometry go to out[0..n). */
+enum {
+  MNL_TBINFO_ACTIVE = 0,          /* 1: the last call of >= 2 steps stepped in pairs */
+  MNL_TBINFO_TB_CELLS = 1,        /* own cells of the two-step items */
+  MNL_TBINFO_TB_BORDER = 2,       /* their border points (upper bound) */
+  MNL_TBINFO_TB_CELLS_MIXED = 3,  /* own cells of the mixed-palette two-step items */
+  MNL_TBINFO_RIM_CELLS = 4,       /* rim cells */
+  MNL_TBINFO_RIM_CELLS_MIXED = 5, /* cells of the mixed-palette rim items */
+  MNL_TBINFO_TB_ITEMS = 6,        /* two-step items */
+  MNL_TBINFO_RIM_ITEMS = 7,       /* rim items */
+  MNL_TBINFO_TB_PLANES = 8,       /* planes of the first two-step item (the longest) */
+  MNL_TBINFO_NARROW_ITEMS = 9,    /* narrow x-face strip items among the rim items */
+  MNL_TBINFO_ENABLED = 10,        /* pairs allowed: set_temporal_blocking / MNL_TB / the tuner */
+  MNL_TBINFO_TB_ZCHUNK = 11,      /* the two-step chunk setting (0: automatic) */
+  MNL_TBINFO_TB_WIDTH = 12,       /* most own columns of a two-step item (124 unless set / tuned) */
+  MNL_TBINFO_TB_POL = 13,         /* 1: polarization chunks stepped inside the pairs */
+  MNL_NUM_TBINFO = 14
+};
 int mnl_fields_tb_info(mnl_fields *f, double *out, int n);
 /* Allow (1, the default; MNL_TB=0 at creation turns it off) or forbid (0) stepping
  * pairs of steps with the two-step kernel.  Results are identical either way. */
 int mnl_fields_set_temporal_blocking(mnl_fields *f, int on);
 /* Scheduling options of the fused step (no reference counterpart; an option only changes how
- * the same per-point arithmetic is scheduled, results are identical): which = 0 the narrow
- * x-face strip body of the temporal-blocking rim (MNL_TB_NARROW; the pair plan is rebuilt at
- * the next step), 1 DFT sampling plans with chi1inv as palette bytes (the plans
- * are rebuilt at the next update), 2 / 3 / 4 the CUs the pair launches / the two-step launch /
- * the rim launches leave free (value = a count, -1 the default), 5 pairs sample DFT
- * monitors from the two-step kernel's compact boxes (MNL_DFT_CMP; the pair plan is rebuilt),
- * 6 planes per rim item of a pair (value; 0 = the one-step chunk length), 7 the chi(2) NR box's
- * E phase beside the tile kernel (MNL_NR_EARLY), 8 planes per two-step item (value; 0 =
- * automatic; MNL_TB_ZCHUNK), 9 the most own columns of a two-step item (value 4..124; 0 = 124,
- * the widest the kernel's 128 columns of lanes hold), 11 pairs of steps with polarization chunks
- * (1, the default), 12 the first rim launch's items other than the narrow x-face
- * strips on a side stream beside the two-step kernel (1, the default; one rank),
- * 16 a pair's step sources and NaN guard in one launch (1, the default; one rank).
- * For in-process A/B measurements (tools/ab_inproc.py).  10, 13, 14 and 15
- * are retired (variants measured slower or no better and since removed):
- * they fail like any unknown number. */
+ * the same per-point arithmetic is scheduled, results are identical).  For in-process A/B
+ * measurements (tools/ab_inproc.py).  A switch takes value 0 / non-zero (all default to 1), the
+ * others a count in the range given; every option but RES, RES_TB2, RES_RIM and SRC_GUARD has
+ * the pair plan rebuilt at the next step.  10, 13, 14 and 15 are retired (variants measured
+ * slower or no better and since removed): they fail like any unknown
+ * number. */
+enum {
+  MNL_SCHED_NARROW = 0,     /* switch: the narrow x-face strip body of the pairs' rim
+                               (MNL_TB_NARROW) */
+  MNL_SCHED_DFT_PAL = 1,    /* switch: DFT sampling plans carry chi1inv as palette bytes (the
+                               plans are rebuilt at the next update) */
+  MNL_SCHED_RES = 2,        /* CUs the pair launches leave free (-1 the default .. 1024) */
+  MNL_SCHED_RES_TB2 = 3,    /* the same for the two-step launch only */
+  MNL_SCHED_RES_RIM = 4,    /* the same for the rim launches only */
+  MNL_SCHED_DFT_CMP = 5,    /* switch: pairs sample DFT monitors from the two-step kernel's
+                               compact boxes (MNL_DFT_CMP) */
+  MNL_SCHED_RIM_ZCHUNK = 6, /* planes per rim item of a pair (0 = the one-step chunk .. 64) */
+  MNL_SCHED_NR_EARLY = 7,   /* switch: the chi(2) NR box's E phase beside the tile kernel
+                               (MNL_NR_EARLY) */
+  MNL_SCHED_TB_ZCHUNK = 8,  /* planes per two-step item (0 = automatic .. 4096; MNL_TB_ZCHUNK) */
+  MNL_SCHED_TB_OX = 9,      /* most own columns of a two-step item (4 .. 124; 0 = 124, the widest
+                               the kernel's 128 columns of lanes hold); the tuner keeps a width
+                               that was set */
+  MNL_SCHED_TB_POL = 11,    /* switch: pairs of steps with polarization chunks */
+  MNL_SCHED_R1_BESIDE = 12, /* switch: the first rim launch's items other than the narrow x-face
+                               strips on a side stream beside the two-step kernel (one rank) */
+  MNL_SCHED_SRC_GUARD = 16  /* switch: a pair's step sources and NaN guard in one launch (one
+                               rank) */
+};
 int mnl_fields_set_schedule(mnl_fields *f, int which, int value);
 
 /* ---- checkpoint (src/fields_dump.cpp, src/structure_dump.cpp) -----------

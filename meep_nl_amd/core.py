@@ -39,6 +39,27 @@ TIME_SINKS = (
 )
 
 
+# The numbers of the diagnostic ABI, mirrors of the enums of include/meep_nl_amd.h
+# (tests/test_abi_tables_cpu.py holds the two together).
+# MNL_SCHED_*: Fields.set_schedule's options; 10, 13, 14 and 15 are retired
+SCHEDULE = {"narrow": 0, "dft_pal": 1, "res": 2, "res_tb2": 3, "res_rim": 4, "dft_cmp": 5,
+            "rim_zchunk": 6, "nr_early": 7, "tb_zchunk": 8, "tb_ox": 9, "tb_pol": 11,
+            "r1_beside": 12, "src_guard": 16}
+# the options that take a count (CUs left free, -1: the default; planes; columns), not a switch
+SCHEDULE_INT = ("res", "res_tb2", "res_rim", "rim_zchunk", "tb_zchunk", "tb_ox")
+# MNL_KSTAT_*: Fields.kernel_stats' kernel groups
+KERNEL_STATS = {"tile": 0, "curl_d": 1, "general": 2, "dft": 3, "e_update": 4, "pairs": 5,
+                "rim": 6, "chain": 7, "ghost_wait": 8, "n2f_far": 9, "n2f_reduce": 10,
+                "dft_get": 11, "dft_load": 12, "dft_scale": 13}
+# MNL_TBINFO_*: the slots of Fields.tb_info, in order
+TB_INFO_KEYS = ("active", "tb_cells", "tb_border", "tb_cells_mixed", "rim_cells",
+                "rim_cells_mixed", "tb_items", "rim_items", "tb_planes", "narrow_items", "enabled",
+                "tb_zchunk", "tb_width", "tb_pol")
+# MNL_MODE_*: the bits of mnl_fields_mode
+MODE_FUSED, MODE_PALETTE, MODE_CONTIG, MODE_TILE, MODE_CONCURRENT = 1, 2, 4, 16, 32
+MODE_FALLBACKS_SHIFT = 8
+
+
 def set_verbosity(level):
     """meep::verbosity of the native library (rank 0's "on time step" lines)."""
     lib().mnl_set_verbosity(int(level))
@@ -536,36 +557,33 @@ class Fields:
         """'single', 'rccl', 'ipc' or 'local' (how ghost planes travel)."""
         return lib().mnl_fields_transport(self.h).decode()
 
-    def fused_active(self):
+    def _mode(self):
+        """The mnl_fields_mode word (MODE_* bits)."""
         v = ctypes.c_int()
         check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
-        return bool(v.value & 1)
+        return v.value
+
+    def fused_active(self):
+        return bool(self._mode() & MODE_FUSED)
 
     def tile_mode(self):
         """True if the fused step runs as one tile kernel (lean + PML bodies): always, in the
         fused mode (it is the only fused step)."""
-        v = ctypes.c_int()
-        check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
-        return bool(v.value & 16)
+        return bool(self._mode() & MODE_TILE)
 
     def fused_concurrent(self):
         """True if the last fused step ran the polarization chunks' general kernel beside the
-        tile kernel on a CU split: kernel_stats(0) then spans both launches."""
-        v = ctypes.c_int()
-        check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
-        return bool(v.value & 32)
+        tile kernel on a CU split: kernel_stats("tile") then spans both launches."""
+        return bool(self._mode() & MODE_CONCURRENT)
 
     def fused_palette(self):
         """True if the fused kernel reads chi1inv through the byte palette."""
-        v = ctypes.c_int()
-        check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
-        return bool(v.value & 2)
+        return bool(self._mode() & MODE_PALETTE)
 
     def alloc_info(self):
         """(contiguous field allocations requested, requests that fell back)."""
-        v = ctypes.c_int()
-        check(lib().mnl_fields_mode(self.h, ctypes.byref(v)))
-        return bool(v.value & 4), (v.value >> 8) & 255
+        m = self._mode()
+        return bool(m & MODE_CONTIG), (m >> MODE_FALLBACKS_SHIFT) & 255
 
     def set_fused(self, allow=True):
         check(lib().mnl_fields_set_fused(self.h, int(allow)))
@@ -574,6 +592,10 @@ class Fields:
         check(lib().mnl_fields_set_profiling(self.h, int(on)))
 
     def kernel_stats(self, which=0):
+        """(launches, total ms, algorithmic bytes per launch) of one kernel group since
+        set_profiling: a name of KERNEL_STATS or its number (mnl_fields_kernel_stats)."""
+        if isinstance(which, str):
+            which = KERNEL_STATS[which]
         n = ctypes.c_longlong()
         ms = ctypes.c_double()
         b = ctypes.c_double()
@@ -587,25 +609,12 @@ class Fields:
         check(lib().mnl_fields_set_temporal_blocking(self.h, 1 if on else 0))
 
     def set_schedule(self, which, value):
-        """Scheduling option (identical results): 'narrow' = the narrow x-face strip body of
-        the temporal-blocking rim, 'dft_pal' = DFT sampling plans carrying chi1inv as palette
-        bytes, 'res' / 'res_tb2' / 'res_rim' = CUs left free by the pair launches (an integer;
-        -1 the default), 'dft_cmp' = pairs sample DFT monitors from the two-step kernel's compact
-        boxes, 'rim_zchunk' = planes per rim item of a pair (an integer; 0 the one-step chunk),
-        'nr_early' = the chi(2) NR box's E phase beside the tile kernel, 'tb_zchunk' = planes per
-        two-step item (an integer; 0 automatic), 'tb_ox' = the most own columns of a two-step
-        item (4..124; 0 = 124), 'tb_pol' = pairs of steps with polarization chunks (their
-        general kernel one step at a time beside the rim launches), 'r1_beside' = the first rim
-        launch's items other than the narrow strips on a side stream beside the two-step
-        kernel, 'src_guard' = a pair's step sources and NaN guard in one launch
-        (mnl_fields_set_schedule; its numbers 10, 13, 14 and 15 are retired)."""
-        idx = {"narrow": 0, "dft_pal": 1, "res": 2, "res_tb2": 3, "res_rim": 4, "dft_cmp": 5,
-               "rim_zchunk": 6, "nr_early": 7, "tb_zchunk": 8, "tb_ox": 9, "tb_pol": 11,
-               "r1_beside": 12, "src_guard": 16}[which]
-        if idx in (2, 3, 4, 6, 8, 9):  # integers: CUs left free (-1: the default), planes, columns
-            check(lib().mnl_fields_set_schedule(self.h, idx, int(value)))
-        else:
-            check(lib().mnl_fields_set_schedule(self.h, idx, 1 if value else 0))
+        """Scheduling option of the fused step (identical results): which is a name of SCHEDULE,
+        value a count for the names of SCHEDULE_INT and a switch for the others.  What each
+        option does, and its range: the MNL_SCHED_* enum of include/meep_nl_amd.h
+        (mnl_fields_set_schedule)."""
+        value = int(value) if which in SCHEDULE_INT else (1 if value else 0)
+        check(lib().mnl_fields_set_schedule(self.h, SCHEDULE[which], value))
 
     def tb_info(self):
         """Temporal blocking of the current fused geometry: dict of
@@ -613,14 +622,11 @@ class Fields:
         points / mixed-palette cells, rim cells / mixed-palette rim cells, item counts, the
         first item's planes, the narrow x-face strip items among the rim items, the
         two-step chunk setting (0: automatic), the most own columns of a two-step item and
-        whether polarization chunks step inside the pairs."""
-        v = (ctypes.c_double * 14)()
-        check(lib().mnl_fields_tb_info(self.h, v, 14))
-        keys = ("active", "tb_cells", "tb_border", "tb_cells_mixed", "rim_cells",
-                "rim_cells_mixed", "tb_items", "rim_items", "tb_planes", "narrow_items", "enabled",
-                "tb_zchunk", "tb_width", "tb_pol")
+        whether polarization chunks step inside the pairs (TB_INFO_KEYS)."""
+        v = (ctypes.c_double * len(TB_INFO_KEYS))()
+        check(lib().mnl_fields_tb_info(self.h, v, len(TB_INFO_KEYS)))
         flags = ("active", "enabled", "tb_pol")
-        return {k: (bool(x) if k in flags else int(x)) for k, x in zip(keys, v)}
+        return {k: (bool(x) if k in flags else int(x)) for k, x in zip(TB_INFO_KEYS, v)}
 
     def traffic_model(self):
         b = ctypes.c_double()

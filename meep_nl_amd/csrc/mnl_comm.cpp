@@ -446,4 +446,37 @@ Comm::~Comm() {
   // events belong to the hub (it may be destroyed before or after us)
 }
 
+const char *rccl_selftest(int n) {
+  char id[128];
+  if (Comm::unique_id(id)) return "ncclGetUniqueId failed";
+  Comm cm;
+  if (cm.init(0, 1, id)) return "RCCL communicator init failed";
+  hipStream_t s;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return "stream";
+  std::vector<double> h(n), back(n);
+  for (int i = 0; i < n; i++) h[i] = 0.5 * i - 3.25;
+  double *a = nullptr, *b = nullptr;
+  const char *err = nullptr;
+  if (hipMalloc(&a, n * sizeof(double)) != hipSuccess ||
+      hipMalloc(&b, n * sizeof(double)) != hipSuccess)
+    err = "hipMalloc failed";
+  if (!err && hipMemcpy(a, h.data(), n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+    err = "upload failed";
+  if (!err && (cm.group_start() || cm.send(a, n, 0, s) || cm.recv(b, n, 0, s) || cm.group_end(s)))
+    err = "grouped send/recv failed";
+  if (!err && (hipStreamSynchronize(s) != hipSuccess ||
+               hipMemcpy(back.data(), b, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+    err = "download failed";
+  if (!err && memcmp(back.data(), h.data(), n * sizeof(double)) != 0)
+    err = "send/recv data mismatch";
+  std::vector<double> red(h);
+  if (!err && cm.allreduce_sum(red.data(), n, s)) err = "allreduce failed";
+  if (!err && memcmp(red.data(), h.data(), n * sizeof(double)) != 0)
+    err = "allreduce data mismatch";
+  if (a) (void)hipFree(a);
+  if (b) (void)hipFree(b);
+  (void)hipStreamDestroy(s);
+  return err;
+}
+
 }  // namespace mnl

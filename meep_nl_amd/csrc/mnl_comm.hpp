@@ -70,6 +70,9 @@ class Comm {
 
 // detail of the last failed RCCL setup call of this thread ("" if none)
 const char *comm_last_error();
+// one-rank RCCL send / recv to self and allreduce of n doubles on the current device through the
+// wrappers above: nullptr, or what failed (not exported from libmnl.so)
+__attribute__((visibility("hidden"))) const char *rccl_selftest(int n);
 LocalHub *local_hub_create(int nranks);
 void local_hub_destroy(LocalHub *h);
 

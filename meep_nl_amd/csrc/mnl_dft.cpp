@@ -817,6 +817,117 @@ int dft_flux_values(mnl_fields *F, int h, double *out) {
   return 0;
 }
 
+// fields::get_dft_array(dft_flux / dft_fields, c, num_freq) (src/dft.cpp:1240-1280):
+// process_dft_component into a whole array (get_dft_component_dims corners; every
+// chunk of c in list order; dft / stored_weight, divided by the loop weight when the
+// chunk stored it; times the interpolation weights of the empty dimensions,
+// src/dft.cpp:908-1040), summed over ranks (sum_to_all: one owner per point), then
+// collapse_array (src/array_slice.cpp:554-601).  out: re/im interleaved.
+int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long dims[3], double *out,
+              long long nout) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  if (dft_flush(F, o)) return -1;  // the buffered updates first
+  if (num_freq < 0 || num_freq > o.nfreq - 1)
+    return fail(("process_dft_component: frequency index " + std::to_string(num_freq) +
+                 " is outside the range of the frequency array of size " +
+                 std::to_string(o.nfreq)).c_str());
+  const mnl_structure &S = F->S;
+  std::vector<const DftChunkH *> L;
+  for (auto &dc : o.E)
+    if (dc.c == c) L.push_back(&dc);
+  for (auto &dc : o.H)
+    if (dc.c == c) L.push_back(&dc);
+  int mn[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, mx[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+  for (auto *dc : L)
+    for (int d = 0; d < 3; d++) mn[d] = std::min(mn[d], dc->is[d]), mx[d] = std::max(mx[d], dc->ie[d]);
+  int r = 0, ds[3] = {0, 0, 0};
+  long long full[3] = {1, 1, 1};
+  if (!L.empty())
+    for (int d = 0; d < 3; d++) {
+      if (!S.has[d]) continue;
+      long long n = (mx[d] - mn[d]) / 2 + 1;
+      if (n > 1) ds[r] = d, full[r++] = n;
+    }
+  int rr = 0;  // collapse_array: directions empty in `where` are summed out
+  long long rd[3] = {1, 1, 1};
+  for (int k = 0; k < r; k++)
+    if (o.wmax[ds[k]] - o.wmin[ds[k]] != 0.0) rd[rr++] = full[k];
+  *rank = rr;
+  for (int k = 0; k < 3; k++) dims[k] = k < rr ? rd[k] : 1;
+  if (!out) return 0;
+  long long rs[3] = {0, 0, 0}, nred = 1;
+  for (int k = r - 1; k >= 0; k--)
+    if (o.wmax[ds[k]] - o.wmin[ds[k]] != 0.0) rs[k] = nred, nred *= full[k];
+  if (r == 0) nred = 0;
+  if (nout < nred) return fail("output buffer too small");
+  for (long long k = 0; k < 2 * nred; k++) out[k] = 0.0;
+  if (r == 0) return 0;
+  const size_t nf = o.nfreq;
+  std::vector<double> v(2 * ((o.npts + 63) & ~size_t(63)) * nf);
+  bool ok = true;
+  if (!v.empty())
+    ok = hipMemcpyAsync(v.data(), o.d_dft, v.size() * 8, hipMemcpyDeviceToHost, F->stream) ==
+             hipSuccess &&
+         hipStreamSynchronize(F->stream) == hipSuccess;
+  if (F->nranks > 1 && F->comm->agree_ok(ok, F->stream))  // every rank fails together
+    return fail(ok ? "get_dft_array: a rank failed" : "get_dft_array: device copy failed");
+  if (!ok) return fail("get_dft_array: device copy failed");
+  long long ntot = 1;
+  for (int k = 0; k < r; k++) ntot *= full[k];
+  std::vector<double> arr(2 * ntot, 0.0);
+  bool empty_dim[3];
+  for (int d = 0; d < 3; d++) empty_dim[d] = S.has[d] && o.wmax[d] - o.wmin[d] == 0.0;
+  const int yd[3] = {S.dim == 2 ? 2 : 0, S.dim == 2 ? 0 : 1, S.dim == 2 ? 1 : 2};
+  for (auto *dc : L) {
+    int n[3];
+    for (int k = 0; k < 3; k++) n[k] = S.has[yd[k]] ? (dc->ie[yd[k]] - dc->is[yd[k]]) / 2 + 1 : 1;
+    size_t pidx = 0;  // chunk_idx: points in LOOP_OVER_IVECS order
+    for (int i1 = 0; i1 < n[0]; i1++)
+      for (int i2 = 0; i2 < n[1]; i2++)
+        for (int i3 = 0; i3 < n[2]; i3++, pidx++) {
+          const size_t pt = dc->p0 + pidx;
+          const int *pj = &o.h_pj[3 * pt];
+          if (pj[0] < 0 && pj[1] < 0 && pj[2] < 0) continue;  // another rank's point
+          const int ii[3] = {i1, i2, i3};
+          int p[3] = {0, 0, 0};
+          for (int k = 0; k < 3; k++)
+            if (S.has[yd[k]]) p[yd[k]] = dc->is[yd[k]] + 2 * ii[k];
+          double wl[3], wi[3];
+          for (int k = 0; k < 3; k++) {
+            const int d = yd[k];
+            wl[k] = loop_w1(dc->s0[d], dc->s1[d], dc->e0[d], dc->e1[d], ii[k], n[k]);
+            wi[k] = empty_dim[d] ? wl[k] : loop_w1(1.0, 1.0, 1.0, 1.0, ii[k], n[k]);
+          }
+          const double w = wl[2] * (wl[1] * ((dc->dV0 + 0.0 * i2) * wl[0]));
+          const double interp_w = wi[2] * (wi[1] * (1.0 * wi[0]));
+          const size_t q = dft_at(o.slot[pt], num_freq, nf);
+          cplx dft_val = cplx(v[2 * q], v[2 * q + 1]) / dc->stored;
+          if (dc->incl && dft_val != 0.0) dft_val /= w;
+          long long oi = 0;
+          for (int k = 0; k < r; k++) oi = oi * full[k] + (p[ds[k]] - mn[ds[k]]) / 2;
+          const cplx val = interp_w * dft_val;
+          arr[2 * oi] = val.real();
+          arr[2 * oi + 1] = val.imag();
+        }
+  }
+  if (F->nranks > 1)
+    for (size_t q = 0; q < arr.size(); q += 1 << 20) {
+      const int n = (int)std::min<size_t>(1 << 20, arr.size() - q);
+      if (timed_allreduce(F, arr.data() + q, n)) return fail("get_dft_array allreduce failed");
+    }
+  for (long long q = 0; q < ntot; q++) {  // collapse_array, in full-index order
+    long long t = q, ri = 0;
+    for (int k = r - 1; k >= 0; k--) {
+      ri += (t % full[k]) * rs[k];
+      t /= full[k];
+    }
+    out[2 * ri] += arr[2 * q];
+    out[2 * ri + 1] += arr[2 * q + 1];
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ DFT data
 // get / load / scale of the accumulated values in list order, replacing
 // save_dft_hdf5 / load_dft_hdf5 (src/dft.cpp:444-496) and dft_chunk::scale_dft (401-405).

@@ -60,6 +60,9 @@ inline int fail(const std::string &m) {
       return fail(std::string("HIP error ") + hipGetErrorString(e_) + " at " #x); \
   } while (0)
 
+// on a declaration shared between the host files: not exported from libmnl.so
+#define MNL_HIDDEN __attribute__((visibility("hidden")))
+
 inline int cdir(int c) { return c % 3; }
 inline int ctype(int c) { return c / 3; }
 
@@ -381,20 +384,25 @@ struct mnl_fields {
   // temporal blocking: pairs of steps as rim (one-step tile kernel) +
   // L2 (two-step kernel) + rim, over three buffer sets
   bool tb_enabled = true;           // MNL_TB=0 at creation: never
-  int tb_zchunk = 0;                // planes per two-step item (0: automatic)
-  int rim_zchunk = 0;               // planes per rim item of a pair (0: fused_zchunk)
-  bool tb_pol_on = true;            // set_schedule 11: no pairs with them
-  bool tb_r1a = true;               // set_schedule 12: R1 after the two-step
-                                    // kernel instead of its non-strip items beside it
+  int tb_zchunk = 0;                // MNL_SCHED_TB_ZCHUNK / MNL_TB_ZCHUNK: planes per two-step
+                                    // item (0: automatic)
+  int rim_zchunk = 0;               // MNL_SCHED_RIM_ZCHUNK: planes per rim item of a pair
+                                    // (0: fused_zchunk)
+  bool tb_pol_on = true;            // MNL_SCHED_TB_POL: grids with polarization chunks step in
+                                    // pairs too (false: one step at a time there)
+  bool tb_r1a = true;               // MNL_SCHED_R1_BESIDE: R1's non-strip items run on a side
+                                    // stream beside the two-step kernel (false: all of R1 after it)
   int tb_rs0 = 0;                   // rim items before the narrow strips (one rank)
-  bool tb_srcguard = true;          // set_schedule 16: a pair's sources
-                                    // and guard as two launches per step (default: one)
+  bool tb_srcguard = true;          // MNL_SCHED_SRC_GUARD: a pair's step sources and NaN guard
+                                    // in one launch (false: two launches per step)
   bool tb_pol = false;              // the pairs step polarization chunks (general kernel, one
                                     // step at a time beside the rim launches; one rank)
-  bool tb_ox_set = false;           // tb_ox set by set_schedule (the tuner keeps it)
-  int tb_ox = 0;                    // most own columns of a two-step item (0: TB_OXW = 124,
-                                    // the 128 columns of lanes less two halo columns per side)
-  bool nr_early = true;             // MNL_NR_EARLY=0: the NR box's E phase after both kernels
+  bool tb_ox_set = false;           // tb_ox set by MNL_SCHED_TB_OX (the tuner keeps it)
+  int tb_ox = 0;                    // MNL_SCHED_TB_OX: most own columns of a two-step item
+                                    // (0: TB_OXW = 124, the 128 columns of lanes less two halo
+                                    // columns per side)
+  bool nr_early = true;             // MNL_SCHED_NR_EARLY / MNL_NR_EARLY: the NR box's E phase
+                                    // runs beside the tile kernel (false: after both kernels)
   unsigned fused_epoch = 0;         // bumped on every entry into the fused mode
   unsigned long long tb_sig = 0;    // inputs of the current plan (0: none)
   bool tb_have = false;             // the current plan has two-step items
@@ -406,14 +414,17 @@ struct mnl_fields {
   TB2Item *d_tb_items = nullptr;
   size_t tb_rcap = 0, tb_gcap = 0, tb_icap = 0;
   bool tb_last = false;     // the last batch of >= 2 steps stepped in pairs (tb_usable)
-  int res_l = -1, res_r = -1;  // schedule options: the same for the two-step / rim launches only
-  int tb_res = -1;          // set_schedule 2: CUs the pairs' persistent launches leave free (-1:
+  int tb_res = -1;          // MNL_SCHED_RES: CUs the pairs' persistent launches leave free (-1:
                             // TB_RES_CUS with several ranks, 0 with one; A/B of the reservation)
+  int res_l = -1, res_r = -1;  // MNL_SCHED_RES_TB2 / MNL_SCHED_RES_RIM: the same for the two-step /
+                               // the rim launches only
   bool tb_oom = false;      // the middle buffer set did not fit: temporal blocking off
   bool tb_oom_test = false; // MNL_TB_OOM=1: its allocation fails (tests)
-  bool tb_narrow = true;    // MNL_TB_NARROW=0: no narrow x-face strip items (A/B)
-  bool dft_pal = true;      // set_schedule 1: DFT sampling plans carry chi1inv as palette bytes
-  bool dft_cmp = true;      // MNL_DFT_CMP=0: pairs sample DFT monitors from the field arrays
+  bool tb_narrow = true;    // MNL_SCHED_NARROW / MNL_TB_NARROW: the pairs' rim has narrow x-face
+                            // strip items (A/B)
+  bool dft_pal = true;      // MNL_SCHED_DFT_PAL: DFT sampling plans carry chi1inv as palette bytes
+  bool dft_cmp = true;      // MNL_SCHED_DFT_CMP / MNL_DFT_CMP: pairs sample DFT monitors from the
+                            // two-step kernel's compact boxes (false: from the field arrays)
   std::vector<TBCmp> tb_cmp;  // the compact DFT boxes of the current pair plan
   int tb_nnarrow = 0;       // narrow x-face strip items of the current plan
   int tb_rfree = 0;         // leading rim items that read no slab-face data (multi-rank)
@@ -671,6 +682,10 @@ bool has_field(const mnl_structure &S, int c);
 int require_component(mnl_fields *F, int c);
 int finalize_fields(mnl_fields *F);
 int initialize_field(mnl_fields *F, int c, const double *host);
+MNL_HIDDEN int sphere_quadrature(int dim, double *xyzw);
+MNL_HIDDEN int set_epsilon_geometry(mnl_structure *s, int device, int nobj, const double *objs,
+                                    double default_eps, int use_averaging, double tol,
+                                    int maxeval);
 
 // ---- mnl_sources.cpp: sources, local indices, get_field
 int build_source_lists(mnl_fields *F);
@@ -722,6 +737,13 @@ int fields_step(mnl_fields *F, int nsteps);
 // ---- mnl_tune.cpp
 int tune(mnl_fields *F, int reps, int *zchunk, int *gen_cus);
 
+// ---- mnl_stats.cpp: kernel statistics and the byte model, tb_info, the mode word
+MNL_HIDDEN int kernel_stats(const mnl_fields *F, int which, long long *launches, double *total_ms,
+                            double *bytes_per_launch);
+MNL_HIDDEN void traffic_model(const mnl_fields *F, double *bpc, double *cells);
+MNL_HIDDEN void tb_info(const mnl_fields *F, double v[MNL_NUM_TBINFO]);
+MNL_HIDDEN int fields_mode(const mnl_fields *F);
+
 // ---- mnl_dft.cpp: loop_in_chunks helpers and DFT monitors
 inline int my_round(double x) { return int(floor(fabs(x) + 0.5) * (x < 0 ? -1 : 1)); }
 inline size_t dft_at(size_t p, size_t i, size_t nf) { return ((p >> 6) * nf + i) * 64 + (p & 63); }
@@ -742,6 +764,8 @@ long long dft_plan_key(const mnl_fields *F);
 int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1);
 bool dft_due(const mnl_fields *F, long long t);
 int dft_flux_values(mnl_fields *F, int h, double *out);
+MNL_HIDDEN int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long dims[3],
+                         double *out, long long nout);
 size_t dft_list_points(const DftFluxH &o, int which);
 int dft_get(mnl_fields *F, int h, int which, double *out, long long n);
 int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign);

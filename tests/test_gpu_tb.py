@@ -166,7 +166,9 @@ def test_retired_schedule_options_rejected(oracle_tb):
     """The schedule variants removed after round 6: their names raise,
     their numbers fail as any unknown number does and change nothing (the run stays bitwise the
     oracle); every surviving name is still accepted."""
+    from meep_nl_amd import core
     from meep_nl_amd._lib import lib
+    assert set(SURVIVING) == set(core.SCHEDULE)  # a new option gets its default here
     p = sc_tb(ProductSim, steps=())
     f = p._fields()
     for name, num in RETIRED.items():
@@ -180,6 +182,40 @@ def test_retired_schedule_options_rejected(oracle_tb):
         p.step(n)
     assert f.tb_info()["active"]
     _same(p, oracle_tb)
+
+
+# the counts among the options: (lowest, highest) accepted, the values next to them that fail,
+# and the text they fail with
+RANGES = {"res": (-1, 1024, (-2, 1025), b"bad reservation"),
+          "res_tb2": (-1, 1024, (-2, 1025), b"bad reservation"),
+          "res_rim": (-1, 1024, (-2, 1025), b"bad reservation"),
+          "rim_zchunk": (0, 64, (-1, 65), b"bad rim chunk"),
+          "tb_zchunk": (0, 4096, (-1, 4097), b"bad two-step chunk"),
+          "tb_ox": (4, 124, (-1, 1, 2, 3, 125), b"bad two-step width")}  # and 0: the default
+
+
+def test_schedule_option_ranges():
+    """A count outside its option's range fails with the option's own message and changes
+    nothing; the ends of the range (and 0 for tb_ox) are accepted; a switch takes any value."""
+    from meep_nl_amd import core
+    from meep_nl_amd._lib import lib
+    assert set(RANGES) == set(core.SCHEDULE_INT)
+    f = sc_tb(ProductSim, steps=())._fields()
+    before = f.tb_info()
+    for name, (lo, hi, outside, text) in RANGES.items():
+        for v in outside:
+            assert lib().mnl_fields_set_schedule(f.h, core.SCHEDULE[name], v) != 0, (name, v)
+            assert lib().mnl_last_error() == b"meep: " + text, (name, v)
+            with pytest.raises(RuntimeError, match=text.decode()):
+                f.set_schedule(name, v)
+    assert f.tb_info() == before
+    for name, (lo, hi, outside, text) in RANGES.items():
+        for v in (lo, hi) + ((0,) if name == "tb_ox" else ()):
+            assert lib().mnl_fields_set_schedule(f.h, core.SCHEDULE[name], v) == 0, (name, v)
+    assert f.tb_info()["tb_zchunk"] == 4096 and f.tb_info()["tb_width"] == 124
+    for name in set(core.SCHEDULE) - set(core.SCHEDULE_INT):
+        for v in (-7, 0, 1, 1 << 20):
+            assert lib().mnl_fields_set_schedule(f.h, core.SCHEDULE[name], v) == 0, (name, v)
 
 
 def sc_tb_volume(make, big, steps=(1, 10, 1, 6), schedule=()):

@@ -38,8 +38,8 @@ def main():
             f.step(a.steps)
             ms.append((time.perf_counter() - t0) / a.steps * 1e3)
         out.append(min(ms))
-        n5, ms5, _ = f.kernel_stats(5)  # pairs: all launches of a pair
-        n6, ms6, _ = f.kernel_stats(6)  # rim launches that run alone
+        n5, ms5, _ = f.kernel_stats("pairs")  # all launches of a pair
+        n6, ms6, _ = f.kernel_stats("rim")  # rim launches that run alone
         parts.append({"pair_ms": ms5 / max(n5, 1), "rim_alone_ms": ms6 / max(n6, 1)})
         print(f"allocation {i}: {min(ms):.4f} ms/step (reps {[round(x, 4) for x in ms]}) "
               f"{parts[-1]}", flush=True)

@@ -104,11 +104,11 @@ def main():
     f.near2far_farfields(h, far)
     best = None
     for _ in range(args.reps):
-        k0, r0 = f.kernel_stats(9), f.kernel_stats(10)
+        k0, r0 = f.kernel_stats("n2f_far"), f.kernel_stats("n2f_reduce")
         w0 = time.perf_counter()
         f.near2far_farfields(h, far)
         wall = (time.perf_counter() - w0) * 1e3
-        k1, r1 = f.kernel_stats(9), f.kernel_stats(10)
+        k1, r1 = f.kernel_stats("n2f_far"), f.kernel_stats("n2f_reduce")
         cur = {"wall_ms": wall, "farfield_kernel_ms": k1[1] - k0[1],
                "reduce_kernel_ms": r1[1] - r0[1], "batches": k1[0] - k0[0]}
         if best is None or cur["wall_ms"] < best["wall_ms"]:
