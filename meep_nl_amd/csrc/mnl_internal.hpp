@@ -1,7 +1,7 @@
 // mnl_internal.hpp -- plain-data structures shared by the host orchestration
-// (mnl_host.cpp, built with g++) and the HIP kernels (mnl_kernels.hip, built
-// with hipcc for gfx950).  No HIP types appear here so both compilers agree
-// on the layout.
+// (the mnl_*.cpp files, built with g++) and the HIP kernels (the mnl_kernels*.hip
+// files, built with hipcc for gfx950), and the declarations of the kernels' launchers.
+// No HIP types appear here so both compilers agree on the layout.
 //
 // Data layout in HBM (DESIGN.md "Layout"): one structure-of-arrays fp64
 // buffer per field component over the rank-local index box
@@ -199,34 +199,18 @@ struct DftChunkDev {
   int d1, d2;
 };
 
-// Host-side launchers implemented in mnl_kernels.hip.
+// The launchers (k_*) of the four kernel files are declared at the end of this file, under one
+// heading per file.
 struct Launch {
   void *stream;  // hipStream_t
 };
 
-// interior: one box on a 3-D grid; shell: all shell boxes in one launch
-// fuseup (shell only): apply the per-point H (after B) / E (after D) update in
-// the same kernel (no B sources; no NR, susceptibilities, integrated sources
-// or D sources in the shell)
-int k_curl(int ft, const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
-           const CurlPlan &p, double courant, void *stream, bool fuseup = false);
-int k_update_h(const BoxList &shell, const DevGrid &g, const DevFields &f, void *stream);
-// update_eh(H_stuff) [+ update_pols(H_stuff) if pols] over box b when H is stored
-// everywhere (f.hall)
-int k_update_hmat(const Box &b, const DevGrid &g, const DevFields &f, int pols, void *stream);
-int k_update_e(const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
-               const ISrcDev &is, int step, bool fuse_pols, void *stream);
-int k_update_pols(const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
-                  void *stream);
-int k_aniso_wall(const DevGrid &g, const DevFields &f, int zero, void *stream);
 // a pair's step tail in one workgroup: D sources (f.Dn; short lists only) then the NaN guard
 constexpr int SRC_GUARD_MAXN = 4096, SRC_GUARD_MAXL = 8;
 struct SrcLayers {
   int n;
   int off[SRC_GUARD_MAXL + 1];
 };
-int k_source(int ft, const DevGrid &g, const DevFields &f, const SrcDev &s, int step,
-             void *stream);
 // Fused step (DESIGN.md "Fused step"): one pass per fields::step() over box G
 // (curl B -> H -> curl D -> E, 3-D, no NR/B sources).  G is tiled into 64 x 14
 // column tiles and z chunks whose bounds come from the host (xb/yb/zb, inclusive
@@ -397,59 +381,12 @@ struct NanTerms {
   long long idx[NAN_MAXT];
   double w[NAN_MAXT];
 };
-// flag[0] |= 1 (and flag[1] = step, once) when the sum is not finite
-int k_nan_check(const NanTerms &t, const double *const E[3], const double *const D[3],
-                const double *const U[3], int *flag, int step, void *stream);
-// a pair's step tail: the D sources of the step into f.Dn, then the guard over E / D (2: the
-// source list is too long for one workgroup -- use k_source + k_nan_check)
-int k_src_guard(const DevFields &f, const SrcDev &s, const NanTerms &t, const double *const E[3],
-                const double *const D[3], const double *const U[3], int *flag, int step,
-                void *stream);
-int k_tb2(const TB2Args &a, void *stream, unsigned long long *bases);
-int k_tb2_uniform(const TB2Args &a, unsigned *flags, void *stream);
-// the tile kernel over an explicit item list (FusedArgs::tgeo boxes), counter line `line`
-int k_tile_items(const FusedArgs &a, const int *items, const int *geo, const unsigned *flags,
-                 int n, int line, void *stream, unsigned long long *bases);
-// per item of that list: the palette word uniform over its footprint, or ~0u
-int k_tile_items_uniform(const FusedArgs &a, const int *items, const int *geo, int n,
-                         unsigned *flags, void *stream);
-// which: general kernel: 1 = all general items, 2 = the general items of chunk 0 (early
-// launch), 3 = the other general items; tile kernel: 4 = all tile items, 5 = tile items of
-// chunk 0 (early launch), 6 = the other tile items (anything else: 2, bad argument).  Every
-// launch reads old / writes new buffers only, on disjoint points, so any order is valid.
-// bases[FUSED_NCTR]: host copy of each counter line's value, advanced by every launch
-// (items + workgroups), so no counter reset (memset launch) is needed per step
-// counter lines (one work queue each): 0-2 tile kernel (all / early / rest), 3 two-step
-// kernel, 4-5 k_tile_items, 8 / 10 general kernel (all and rest / early)
+// counter lines of the persistent kernels (one work queue each): 0-2 tile kernel (all / early /
+// rest), 3 two-step kernel, 4-5 k_tile_items, 8 / 10 general kernel (all and rest / early)
 constexpr int FUSED_NCTR = 16;
-int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bases);
-// per tile / general item, the chi1inv palette word when it is uniform over the cells the
-// item uses, else ~0u (flags: one word per item); the kernels then read one cached word
-// instead of a palette index per cell
-int k_tile_uniform(const FusedArgs &a, unsigned *flags, void *stream);
-int k_general_uniform(const FusedArgs &a, unsigned *flags, void *stream);
-int k_cu_count();
-int k_build_uidx(unsigned *uidx, const double *const u[3], const double *tab, const int n[3],
-                 const Box &F, long long st1, long long st2, int *bad, void *stream);
-// E = chi1inv * D over box F (leaving fused mode / readout)
-int k_materialize_e(const Box &F, const DevGrid &g, const DevFields &f, void *stream);
-int k_fill(double *p, double v, size_t n, void *stream);
-// dft_chunk::update_dft for every point of one flux object (src/dft.cpp:265-300),
-// blocked over up to DFT_KB updates: sample the averaged field of one update
-// into fr, then accumulate n buffered updates (phases: n rows, rstride
-// complex values apart) into the DFT array
 constexpr int DFT_KB = 32;  // updates buffered per accumulation (the DFT array is read and
                             // written once per DFT_KB updates)
 constexpr int DFT_FT = 8;   // frequency tile of the accumulation
-int k_dft_sample(const int *pj, const double *pw, const int *pch, const DftChunkDev *ch, double *fr,
-                 long long npts, const DevGrid &g, const DevFields &f, void *stream);
-// sampling plan of one flux object (per point: the first Yee index, a 16-bit selector, the
-// palette bytes and the doubles of the chi1inv of its implicit-E values; see
-// dft_plan_kernel), then the sample of one update of every flux object due (one launch)
-int k_dft_plan(const int *pj, const int *pch, const DftChunkDev *ch, long long npts,
-               const DevGrid &g, const DevFields &f, const unsigned *uidx, const double *utab,
-               int *sidx, unsigned short *ssel, unsigned *spal, void *su, int *bad,
-               const Box &cbox, int *sci, void *stream);
 constexpr int DFT_MAXJ = 8;  // flux objects per sample launch
 struct DftSampleJob {
   const int *sidx;
@@ -472,40 +409,6 @@ struct DftSampleJobs {
   long long nblk;   // workgroups of all jobs
   long long sd[3];  // set by k_dft_sample_jobs (grid strides per direction)
 };
-int k_dft_sample_jobs(const DftSampleJobs &J, const DevGrid &g, const DevFields &f,
-                      const double *utab, void *stream);
-int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, int n,
-                const double *ph, long long rstride, int nfreq, long long npts, void *stream);
-// DFT data in list order (DESIGN.md section 29): inv[slot] = index in the list or -1, for
-// nslots padded to 64; out / in are [list point][freq] complex on the device
-int k_dft_gather(const double *dft, const int *inv, double *out, int nfreq, long long nslots,
-                 void *stream);
-int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, int nfreq,
-                  long long nslots, void *stream);
-int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream);
-int k_init_add(double *dst, double *alt, const double *src, const DevGrid &g, const DevFields &f,
-               int comp_type, int comp_dir, void *stream);
-int k_copy(double *dst, const double *src, long long n, void *stream);
-int k_average(double *f, const double *bk, long long n, void *stream);
-int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,
-             const DevFields &f, int type, int c, const EBox &box, const double *wt,
-             double *partial, int nblocks, void *stream);
-int k_from_canonical(double *dst, const double *src, const DevGrid &g, int comp_type,
-                     int comp_dir, int zlo_glob, void *stream);
-int k_to_canonical(double *dst, const double *src, const double *hsep, const DevGrid &g,
-                   int comp_type, int comp_dir, const DevFields &f, const Box *fusedF,
-                   const double *dsrc, const double *usrc, void *stream);
-// the same into a box of the whole-cell array: global indices blo..bhi per
-// direction, destination strides bs (entries this rank does not own untouched)
-int k_to_box(double *dst, const double *src, const double *hsep, const DevGrid &g, int comp_type,
-             int comp_dir, const DevFields &f, const Box *fusedF, const double *dsrc,
-             const double *usrc, const int blo[3], const int bhi[3], const long long bs[3],
-             void *stream);
-// bounding box (local indices per direction, as Pt::j) of the points where any array is nonzero
-int k_nonzero_box(const double *const a[3], const DevGrid &g, int *dev_box6, void *stream);
-// structure::set_epsilon with a geometric material function (subpixel averaging),
-// src/anisotropic_averaging.cpp:58-298: one thread per canonical point of E comp c
-// one deferred chi(2) Newton-Raphson problem (run_nr after a failed first attempt)
 // Seed of the deterministic stand-in for the std::random_device fallback of runNR
 // (newton_raphson.cpp:196-206, 331-336): a counter-based value of the point's global
 // half-coordinates q (relative to the cell's little corner; 0 for absent directions), the
@@ -525,6 +428,7 @@ inline unsigned long long nr_voxel_seed(long long q0, long long q1, long long q2
   return h;
 }
 
+// one deferred chi(2) Newton-Raphson problem (run_nr after a failed first attempt)
 struct NRHard {
   double p[15];       // NRP p1, p2, p3 (A, B, F, G, H each)
   double seed[3];     // the first attempt's seeds
@@ -534,8 +438,9 @@ struct NRHard {
   unsigned long long rng;
   int d;
 };
-int k_nr_hard(const DevFields &f, void *stream);
 
+// structure::set_epsilon with a geometric material function (subpixel averaging),
+// src/anisotropic_averaging.cpp:58-298: one thread per canonical point of E comp c
 struct GeoObj {
   int kind;       // 0 block (p = size), 1 sphere (p0 = radius), 2 cylinder (p0 = radius,
                   // p1 = height, p2 = axis 0/1/2)
@@ -557,10 +462,6 @@ struct AvgArgs {
   double *out[3];      // rows d = 0..2 over the canonical grid (null: not wanted)
   long long ntot;
 };
-int k_avg_chi1inv(const AvgArgs &a, void *stream);
-int k_box_fill(double *dst, const DevGrid &g, int comp_type, int comp_dir, const double *pos_lo,
-               const double *pos_hi, double value, int invert, double a, const int *io,
-               void *stream);
 
 // dft_near2far::farfield_lowlevel (src/near2far.cpp:340-387) with green3d (133-187) for a batch
 // of far points: every workgroup sums its fixed range of this rank's slots for a tile of
@@ -590,7 +491,119 @@ struct N2FArgs {
 // frequency tile x far-point block, by measurement (2x2 at 2 waves per
 // SIMD beat 4x2, 2x4 at 1 wave and 1x2 at 3 waves)
 constexpr int N2F_FT = 2, N2F_NP = 2;
+
+// =============================================================== launchers
+// Host-side launchers of the kernels, one heading per kernel file.  Each but k_cu_count
+// returns 0, or a non-zero code when an argument is bad or the launch failed.
+
+// ---- mnl_kernels.hip: what a step launches
+// interior: one box on a 3-D grid; shell: all shell boxes in one launch
+// fuseup (shell only): apply the per-point H (after B) / E (after D) update in
+// the same kernel (no B sources; no NR, susceptibilities, integrated sources
+// or D sources in the shell)
+int k_curl(int ft, const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
+           const CurlPlan &p, double courant, void *stream, bool fuseup = false);
+int k_update_h(const BoxList &shell, const DevGrid &g, const DevFields &f, void *stream);
+// update_eh(H_stuff) [+ update_pols(H_stuff) if pols] over box b when H is stored
+// everywhere (f.hall)
+int k_update_hmat(const Box &b, const DevGrid &g, const DevFields &f, int pols, void *stream);
+int k_update_e(const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
+               const ISrcDev &is, int step, bool fuse_pols, void *stream);
+int k_nr_hard(const DevFields &f, void *stream);
+int k_update_pols(const Box &in, const BoxList *shell, const DevGrid &g, const DevFields &f,
+                  void *stream);
+int k_aniso_wall(const DevGrid &g, const DevFields &f, int zero, void *stream);
+int k_source(int ft, const DevGrid &g, const DevFields &f, const SrcDev &s, int step,
+             void *stream);
+// flag[0] |= 1 (and flag[1] = step, once) when the sum is not finite
+int k_nan_check(const NanTerms &t, const double *const E[3], const double *const D[3],
+                const double *const U[3], int *flag, int step, void *stream);
+// a pair's step tail: the D sources of the step into f.Dn, then the guard over E / D (2: the
+// source list is too long for one workgroup -- use k_source + k_nan_check)
+int k_src_guard(const DevFields &f, const SrcDev &s, const NanTerms &t, const double *const E[3],
+                const double *const D[3], const double *const U[3], int *flag, int step,
+                void *stream);
+// which: general kernel: 1 = all general items, 2 = the general items of chunk 0 (early
+// launch), 3 = the other general items; tile kernel: 4 = all tile items, 5 = tile items of
+// chunk 0 (early launch), 6 = the other tile items (anything else: 2, bad argument).  Every
+// launch reads old / writes new buffers only, on disjoint points, so any order is valid.
+// bases[FUSED_NCTR]: host copy of each counter line's value, advanced by every launch
+// (items + workgroups), so no counter reset (memset launch) is needed per step
+int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bases);
+// the tile kernel over an explicit item list (FusedArgs::tgeo boxes), counter line `line`
+int k_tile_items(const FusedArgs &a, const int *items, const int *geo, const unsigned *flags,
+                 int n, int line, void *stream, unsigned long long *bases);
+int k_tb2(const TB2Args &a, void *stream, unsigned long long *bases);
+// per tile / general / two-step item, the chi1inv palette word when it is uniform over the
+// cells the item uses, else ~0u (flags: one word per item); the kernels then read one cached
+// word instead of a palette index per cell
+int k_tile_uniform(const FusedArgs &a, unsigned *flags, void *stream);
+int k_general_uniform(const FusedArgs &a, unsigned *flags, void *stream);
+int k_tile_items_uniform(const FusedArgs &a, const int *items, const int *geo, int n,
+                         unsigned *flags, void *stream);
+int k_tb2_uniform(const TB2Args &a, unsigned *flags, void *stream);
+// E = chi1inv * D over box F (leaving fused mode / readout)
+int k_materialize_e(const Box &F, const DevGrid &g, const DevFields &f, void *stream);
+// CUs of the current device (the persistent kernels launch one workgroup per CU)
+int k_cu_count();
+
+// ---- mnl_kernels_setup.hip: launched once, by mnl_setup.cpp and the planning code
+int k_avg_chi1inv(const AvgArgs &a, void *stream);
+int k_box_fill(double *dst, const DevGrid &g, int comp_type, int comp_dir, const double *pos_lo,
+               const double *pos_hi, double value, int invert, double a, const int *io,
+               void *stream);
+// bounding box (local indices per direction, as Pt::j) of the points where any array is nonzero
+int k_nonzero_box(const double *const a[3], const DevGrid &g, int *dev_box6, void *stream);
+int k_build_uidx(unsigned *uidx, const double *const u[3], const double *tab, const int n[3],
+                 const Box &F, long long st1, long long st2, int *bad, void *stream);
+int k_from_canonical(double *dst, const double *src, const DevGrid &g, int comp_type,
+                     int comp_dir, int zlo_glob, void *stream);
+int k_init_add(double *dst, double *alt, const double *src, const DevGrid &g, const DevFields &f,
+               int comp_type, int comp_dir, void *stream);
+
+// ---- mnl_kernels_dft.hip: DFT monitors and the near-to-far-field transform
+// dft_chunk::update_dft for every point of one flux object (src/dft.cpp:265-300),
+// blocked over up to DFT_KB updates: sample the averaged field of one update
+// into fr, then accumulate n buffered updates (phases: n rows, rstride
+// complex values apart) into the DFT array
+int k_dft_sample(const int *pj, const double *pw, const int *pch, const DftChunkDev *ch, double *fr,
+                 long long npts, const DevGrid &g, const DevFields &f, void *stream);
+int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, int n,
+                const double *ph, long long rstride, int nfreq, long long npts, void *stream);
+// sampling plan of one flux object (per point: the first Yee index, a 16-bit selector, the
+// palette bytes and the doubles of the chi1inv of its implicit-E values; see
+// dft_plan_kernel), then the sample of one update of every flux object due (one launch)
+int k_dft_plan(const int *pj, const int *pch, const DftChunkDev *ch, long long npts,
+               const DevGrid &g, const DevFields &f, const unsigned *uidx, const double *utab,
+               int *sidx, unsigned short *ssel, unsigned *spal, void *su, int *bad,
+               const Box &cbox, int *sci, void *stream);
+int k_dft_sample_jobs(const DftSampleJobs &J, const DevGrid &g, const DevFields &f,
+                      const double *utab, void *stream);
+// DFT data in list order (DESIGN.md section 29): inv[slot] = index in the list or -1, for
+// nslots padded to 64; out / in are [list point][freq] complex on the device
+int k_dft_gather(const double *dft, const int *inv, double *out, int nfreq, long long nslots,
+                 void *stream);
+int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, int nfreq,
+                  long long nslots, void *stream);
+int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream);
 int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream);
 int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream);
+
+// ---- mnl_kernels_io.hip: what mnl_io.cpp and the ABI's getters launch
+int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,
+             const DevFields &f, int type, int c, const EBox &box, const double *wt,
+             double *partial, int nblocks, void *stream);
+int k_to_canonical(double *dst, const double *src, const double *hsep, const DevGrid &g,
+                   int comp_type, int comp_dir, const DevFields &f, const Box *fusedF,
+                   const double *dsrc, const double *usrc, void *stream);
+// the same into a box of the whole-cell array: global indices blo..bhi per
+// direction, destination strides bs (entries this rank does not own untouched)
+int k_to_box(double *dst, const double *src, const double *hsep, const DevGrid &g, int comp_type,
+             int comp_dir, const DevFields &f, const Box *fusedF, const double *dsrc,
+             const double *usrc, const int blo[3], const int bhi[3], const long long bs[3],
+             void *stream);
+int k_average(double *f, const double *bk, long long n, void *stream);
+int k_copy(double *dst, const double *src, long long n, void *stream);
+int k_fill(double *p, double v, size_t n, void *stream);
 
 }  // namespace mnl

@@ -1,4 +1,9 @@
-// mnl_kernels.hip -- gfx950 kernels of the fields::step() hot path.
+// mnl_kernels.hip -- gfx950 kernels a fields::step() launches, and their launchers: the
+// per-sub-step kernels, the fused general / tile / two-step kernels with their footprint
+// uniformity kernels, the NaN guard and materialize_e.  Nothing else: the hash of this file
+// keys the committed HBM-traffic profile of the step (bench.py, tools/pmc_pairs.py).  Setup,
+// DFT / far-field and I/O kernels are in mnl_kernels_setup.hip, mnl_kernels_dft.hip and
+// mnl_kernels_io.hip; the point mapping they share with this file is in mnl_device.hpp.
 //
 // Global-grid formulation of the reference's chunked update:
 // the reference splits PML regions into their own chunks and runs a different
@@ -11,30 +16,11 @@
 // -ffp-contract=off, so results are bitwise those of the CPU reference.
 //
 // All kernels are HBM-bound fp64 stencils (0.1-0.2 flop/byte): no MFMA.
-#include <hip/hip_runtime.h>
+#include <type_traits>
 
-#include "mnl_internal.hpp"
-
-// Every kernel here is written for 64-lane wavefronts (gfx950): the fused bodies map one
-// 64-column row to a wave, nr_hard_kernel runs one attempt per lane with a 64-bit ballot.
-#if defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
-#error "mnl_kernels.hip needs wave64 (build for gfx950)"
-#endif
+#include "mnl_device.hpp"
 
 namespace mnl {
-
-#define MNL_BX 64
-#define MNL_BY 4
-
-__device__ __forceinline__ int shift_of(int type, int c, int d) {
-  // grid_volume::iyee_shift (src/meep/vec.hpp:1133-1141)
-  return (type == T_E || type == T_D) ? (d == c) : (d != c);
-}
-
-struct Pt {
-  int j[3];       // local index per direction (0 for absent)
-  long long idx;  // linear index
-};
 
 __device__ __forceinline__ bool make_pt(const Box &b, const DevGrid &g, Pt &p) {
   int i0 = b.lo[0] + blockIdx.x * MNL_BX + threadIdx.x;
@@ -72,49 +58,6 @@ __device__ __forceinline__ bool make_pt_lin(const BoxList &bl, const DevGrid &g,
 template <bool SHELL>
 __device__ __forceinline__ bool map_pt(const Box &b, const BoxList &bl, const DevGrid &g, Pt &p) {
   return SHELL ? make_pt_lin(bl, g, p) : make_pt(b, g, p);
-}
-
-// little_owned_corner0 .. big_corner (src/meep/vec.hpp:1102-1104), with the
-// metallic wall plane left untouched (it is zeroed by zero_metal in the
-// reference, src/boundaries.cpp:304-339, and never becomes nonzero).
-__device__ __forceinline__ bool owned(const DevGrid &g, int type, int c, const Pt &p) {
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    if (g.ax[d] < 0) continue;
-    if (shift_of(type, c, d)) {
-      if (p.j[d] < g.owned_lo_sh[d] || p.j[d] > g.owned_hi_sh[d]) return false;
-    } else {
-      if (p.j[d] < g.owned_lo_un[d] || p.j[d] > g.owned_hi_un[d]) return false;
-    }
-  }
-  return true;
-}
-
-// global half-coordinate (relative to the cell's little corner) of a point
-__device__ __forceinline__ int qcoord(const DevGrid &g, const Pt &p, int type, int c, int d) {
-  return 2 * (p.j[d] + g.off[d]) + shift_of(type, c, d);
-}
-
-__device__ __forceinline__ bool pml_at(const DevFields &f, const DevGrid &g, int d, int q) {
-  return g.ax[d] >= 0 && f.pml.flag[d] != nullptr && f.pml.flag[d][q] != 0;
-}
-
-// Fused mode: E of comp c at p is not stored but equals chi1inv * D (DESIGN.md
-// "Fused step"): p inside the fused domain G, E_c owned there and not in a
-// PML chunk along c (where E carries W-form history and is stored).
-__device__ __forceinline__ bool e_implicit(const DevFields &f, const DevGrid &g, int c,
-                                           const Pt &p) {
-  if (!f.fused) return false;
-#pragma unroll
-  for (int d = 0; d < 3; d++)
-    if (p.j[d] < f.fG.lo[d] || p.j[d] > f.fG.hi[d]) return false;
-  for (int k = 0; k < f.npol; k++) {  // stored inside a polarization's nonzero box
-    const Box &b = f.pol[k].nz;
-    if (p.j[0] >= b.lo[0] && p.j[0] <= b.hi[0] && p.j[1] >= b.lo[1] && p.j[1] <= b.hi[1] &&
-        p.j[2] >= b.lo[2] && p.j[2] <= b.hi[2])
-      return false;
-  }
-  return owned(g, T_E, c, p) && !pml_at(f, g, c, qcoord(g, p, T_E, c, c));
 }
 
 // conductivity allocated in the reference chunk that owns point p (zone box)
@@ -1084,314 +1027,52 @@ __global__ void source_kernel(Ptr3 pt, SrcDev s, int k0, int k1) {
   pt.p[c][i] -= pt.ci[c] ? v * pt.ci[c][i] : v;
 }
 
-__global__ void fill_kernel(double *p, double v, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
-// canonical (Z fastest, whole cell) <-> device layout (rank-local box)
-__global__ void from_canonical_kernel(double *dst, const double *src, DevGrid g, long long cs0,
-                                      long long cs1, long long cs2) {
-  int i0 = blockIdx.x * MNL_BX + threadIdx.x;
-  int i1 = blockIdx.y * MNL_BY + threadIdx.y;
-  int i2 = blockIdx.z;
-  if (i0 >= g.N[0] || i1 >= g.N[1]) return;
-  int ii[3] = {i0, i1, i2};
-  long long cidx = 0;
-  long long cs[3] = {cs0, cs1, cs2};
-  for (int d = 0; d < 3; d++)
-    if (g.ax[d] >= 0) cidx += (long long)(ii[g.ax[d]] + g.off[d]) * cs[d];
-  dst[(long long)i0 + i1 * g.st[1] + i2 * g.st[2]] = src[cidx];
-}
-
-// Rank-owned entries of one component into a box of the whole-cell array
-// (global indices blo..bhi per direction, strides bs); the launch covers the
-// local index range lo.. of that box.
-__global__ void to_box_kernel(double *dst, const double *src, const double *hsep, DevGrid g,
-                              DevFields f, int type, int c, int l0, int l1, int l2, int n0, int n1,
-                              long long bs0, long long bs1, long long bs2, int blo0, int blo1,
-                              int blo2, int use_fb, const double *dsrc, const double *usrc) {
-  const int i0 = l0 + blockIdx.x * MNL_BX + threadIdx.x;
-  const int i1 = l1 + blockIdx.y * MNL_BY + threadIdx.y;
-  const int i2 = l2 + blockIdx.z;
-  if (i0 >= l0 + n0 || i1 >= l1 + n1) return;
-  int ii[3] = {i0, i1, i2};
-  Pt p;
-  for (int d = 0; d < 3; d++) p.j[d] = g.ax[d] >= 0 ? ii[g.ax[d]] : 0;
-  // rank-owned planes only along every axis (ghost entries are filled by
-  // their owner; non-owned boundary entries are 0 in the reference).
-  for (int d = 0; d < 3; d++) {
-    if (g.ax[d] < 0) continue;
-    int sh = shift_of(type, c, d);
-    int lo = sh ? g.owned_lo_sh[d] : g.owned_lo_un[d];
-    int hi = sh ? g.owned_hi_sh[d] : g.owned_hi_un[d];
-    if (!sh && g.wall[d] && p.j[d] + g.off[d] == g.nglob[d]) hi = p.j[d];  // wall plane (= 0)
-    if (p.j[d] < lo || p.j[d] > hi) return;
-  }
-  const long long bs[3] = {bs0, bs1, bs2};
-  const int blo[3] = {blo0, blo1, blo2};
-  long long cidx = 0;
-  for (int d = 0; d < 3; d++)
-    if (g.ax[d] >= 0) cidx += (long long)(p.j[d] + g.off[d] - blo[d]) * bs[d];
-  long long i = (long long)i0 + i1 * g.st[1] + i2 * g.st[2];
-  double v = src[i];
-  if (hsep && (f.hall || pml_at(f, g, c, qcoord(g, p, T_H, c, c)))) v = hsep[i];
-  p.idx = i;
-  if (use_fb && type == T_E && e_implicit(f, g, c, p))  // fused: E = chi1inv * D (not stored)
-    v = usrc ? (dsrc[i] * usrc[i]) : dsrc[i];
-  dst[cidx] = v;
-}
-
-__global__ void box_fill_kernel(double *dst, DevGrid g, int type, int c, double x0, double x1,
-                                double y0, double y1, double z0, double z1, double value,
-                                int invert, double a, int io0, int io1, int io2) {
-  int i0 = blockIdx.x * MNL_BX + threadIdx.x;
-  int i1 = blockIdx.y * MNL_BY + threadIdx.y;
-  int i2 = blockIdx.z;
-  if (i0 >= g.N[0] || i1 >= g.N[1]) return;
-  int ii[3] = {i0, i1, i2};
-  double lo[3] = {x0, y0, z0}, hi[3] = {x1, y1, z1};
-  int io[3] = {io0, io1, io2};
-  for (int d = 0; d < 3; d++) {
-    if (g.ax[d] < 0) continue;
-    int jj = ii[g.ax[d]] + g.off[d];
-    double pos = (io[d] + 2 * jj + shift_of(type, c, d)) * (0.5 * (1.0 / a));
-    if (pos < lo[d] || pos > hi[d]) return;
-  }
-  dst[(long long)i0 + i1 * g.st[1] + i2 * g.st[2]] = invert ? 1.0 / value : value;
-}
-
-// ------------------------------------------------------ subpixel averaging
-// structure_chunk::set_chi1inv with a material_function (src/anisotropic_averaging.cpp:
-// 221-298) over a list of geometric objects of isotropic permittivity (later objects
-// win): per point the rownum'th row of the effective tensor at dV(here) (diagonal
-// entry) and at dV(here - shift1) (off-diagonal entries), material_function::
-// eff_chi1inv_row / normal_vector (58-219), in the reference's operation order.
-__device__ double geo_chi1p1(const AvgArgs &A, const double r[3]) {
-  for (int o = A.nobj - 1; o >= 0; o--) {
-    const GeoObj &g = A.objs[o];
-    const double dx = r[0] - g.c[0], dy = r[1] - g.c[1], dz = r[2] - g.c[2];
-    bool in;
-    if (g.kind == 0) {
-      in = fabs(dx) <= 0.5 * g.p[0] && fabs(dy) <= 0.5 * g.p[1] && fabs(dz) <= 0.5 * g.p[2];
-    } else if (g.kind == 1) {
-      in = dx * dx + dy * dy + dz * dz <= g.p[0] * g.p[0];
-    } else {
-      const int ax = (int)g.p[2];
-      const double da = ax == 0 ? dx : ax == 1 ? dy : dz;
-      const double u = ax == 0 ? dy : dx, v = ax == 2 ? dy : dz;
-      in = fabs(da) <= 0.5 * g.p[1] && u * u + v * v <= g.p[0] * g.p[0];
-    }
-    if (in) return g.eps;
-  }
-  return A.default_eps;
-}
-
-__device__ void eff_chi1inv_row(const AvgArgs &A, const double vmin[3], const double vmax[3],
-                                double row[3]) {
-  const int rownum = A.c;
-  double cen[3] = {0, 0, 0};
-  for (int k = 0; k < A.ndir; k++) {
-    const int d = A.dirs[k];
-    cen[d] = (vmin[d] + vmax[d]) * 0.5;
-  }
-  double meps = 1, minveps = 1;
-  double grad[3] = {0, 0, 0};
-  if (A.maxeval) {
-    // normal_vector: sphere quadrature of diameter R around the centre
-    double R = 0.0;
-    for (int k = 0; k < A.ndir; k++) R = fmax(R, vmax[A.dirs[k]] - vmin[A.dirs[k]]);
-    const int nd = A.ndir, min_iters = 1 << nd;
-    const double *q = A.quad + (nd - 1) * AVG_MAXQ * 4;
-    double prev = 0;
-    bool break_early = true, uniform = false;
-    for (int i = 0; i < A.nq[nd - 1]; ++i) {
-      const double w = q[4 * i + 3];
-      double pt[3] = {0, 0, 0};
-      if (nd == 1) {
-        pt[2] = cen[2] + q[4 * i + 2] * R;
-      } else {
-        for (int k = 0; k < nd; k++) pt[k] = cen[k] + q[4 * i + k] * R;
-      }
-      const double val = geo_chi1p1(A, pt);
-      if (i > 0 && i < min_iters) {
-        if (val != prev) break_early = false;
-        if (i == min_iters - 1 && break_early) {
-          uniform = true;
-          break;
-        }
-      }
-      prev = val;
-      for (int k = 0; k < nd; k++) {
-        const int d = A.dirs[k];
-        grad[d] += (pt[d] - cen[d]) * (w * val);
-      }
-    }
-    double g2 = 0.0;
-    for (int k = 0; k < nd; k++) g2 += grad[A.dirs[k]] * grad[A.dirs[k]];
-    if (!uniform && !(sqrt(g2) < 1e-8)) {
-      double dd[3] = {0, 0, 0};
-      for (int k = 0; k < nd; k++) dd[A.dirs[k]] = vmax[A.dirs[k]] - vmin[A.dirs[k]];
-      int ms = 10, iter = 0;
-      double old_meps = 0, old_minveps = 0;
-      bool trivial = false;
-      for (;;) {
-        const bool go = nd == 3 ? (fabs(meps - old_meps) > A.tol * fabs(old_meps)) &&
-                                      (fabs(minveps - old_minveps) > A.tol * fabs(old_minveps))
-                                : (fabs(meps - old_meps) > A.tol * old_meps) &&
-                                      (fabs(minveps - old_minveps) > A.tol * old_minveps);
-        if (!go) break;
-        old_meps = meps;
-        old_minveps = minveps;
-        meps = minveps = 0;
-        if (nd == 3) {
-          for (int k = 0; k < ms && !trivial; k++)
-            for (int j = 0; j < ms && !trivial; j++)
-              for (int i = 0; i < ms; i++) {
-                const double pt[3] = {vmin[0] + i * dd[0] / ms, vmin[1] + j * dd[1] / ms,
-                                      vmin[2] + k * dd[2] / ms};
-                const double ep = geo_chi1p1(A, pt);
-                if (ep < 0) {
-                  trivial = true;
-                  break;
-                }
-                meps += ep;
-                minveps += 1 / ep;
-              }
-          if (trivial) break;
-          meps /= ms * ms * ms;
-          minveps /= ms * ms * ms;
-          ms *= 2;
-          if (A.maxeval && (iter += ms * ms * ms) >= A.maxeval) break;
-        } else if (nd == 2) {
-          for (int j = 0; j < ms && !trivial; j++)
-            for (int i = 0; i < ms; i++) {
-              const double pt[3] = {vmin[0] + i * dd[0] / ms, vmin[1] + j * dd[1] / ms, 0.0};
-              const double ep = geo_chi1p1(A, pt);
-              if (ep < 0) {
-                trivial = true;
-                break;
-              }
-              meps += ep;
-              minveps += 1 / ep;
-            }
-          if (trivial) break;
-          meps /= ms * ms;
-          minveps /= ms * ms;
-          ms *= 2;
-          if (A.maxeval && (iter += ms * ms) >= A.maxeval) break;
-        } else {
-          bool neg = false;
-          for (int i = 0; i < ms; i++) {
-            const double pt[3] = {0.0, 0.0, vmin[2] + i * dd[2] / ms};
-            const double ep = geo_chi1p1(A, pt);
-            if (ep < 0) {
-              meps = geo_chi1p1(A, cen);
-              minveps = 1 / meps;
-              neg = true;
-              break;
-            }
-            meps += ep;
-            minveps += 1 / ep;
-          }
-          if (neg) break;
-          meps /= ms;
-          minveps /= ms;
-          ms *= 2;
-          if (A.maxeval && (iter += ms * ms) >= A.maxeval) break;
-        }
-      }
-      if (!trivial) {
-        double n[3] = {0, 0, 0};
-        const double nabsinv = 1.0 / sqrt(g2);
-        for (int k = 0; k < nd; k++) n[A.dirs[k]] = grad[A.dirs[k]] * nabsinv;
-        for (int i = 0; i < 3; ++i) row[i] = n[rownum] * n[i] * (minveps - 1 / meps);
-        row[rownum] += 1 / meps;
-        return;
-      }
-    }
-  }
-  row[0] = row[1] = row[2] = 0.0;
-  row[rownum] = 1 / geo_chi1p1(A, cen);
-}
-
-__global__ void avg_chi1inv_kernel(AvgArgs A) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.ntot) return;
-  // canonical index -> point (z fastest, then y, then x)
-  int idx[3] = {0, 0, 0};
-  long long r = i;
-  for (int d = 2; d >= 0; d--)
-    if (A.has[d]) {
-      idx[d] = (int)(r % (A.n[d] + 1));
-      r /= A.n[d] + 1;
-    }
-  const double h = 0.5 * A.inva;  // grid_volume::dV: hinva = 0.5 * inva * diameter (1.0)
-  double vmin[3] = {0, 0, 0}, vmax[3] = {0, 0, 0}, omin[3] = {0, 0, 0}, omax[3] = {0, 0, 0};
-  for (int k = 0; k < A.ndir; k++) {
-    const int d = A.dirs[k];
-    const int here = A.io[d] + 2 * idx[d] + (d == A.c ? 1 : 0);
-    const double hp = here * (0.5 * A.inva), hm = (here - (d == A.c ? 1 : 0)) * (0.5 * A.inva);
-    vmax[d] = hp + h;
-    vmin[d] = hp - h;
-    omax[d] = hm + h;  // here - shift1 (E: shifted back half a pixel along c)
-    omin[d] = hm - h;
-  }
-  double row[3];
-  eff_chi1inv_row(A, vmin, vmax, row);
-  if (A.out[A.c]) A.out[A.c][i] = row[A.c];
-  bool off = false;
-  for (int d = 0; d < 3; d++) off = off || (d != A.c && A.out[d]);
-  if (!off) return;
-  eff_chi1inv_row(A, omin, omax, row);
-  for (int d = 0; d < 3; d++)
-    if (d != A.c && A.out[d]) A.out[d][i] = row[d];
-}
-
 // ----------------------------------------------------------------- launchers
 static dim3 grid_for(const Box &b) {
   int n0 = b.hi[0] - b.lo[0] + 1, n1 = b.hi[1] - b.lo[1] + 1, n2 = b.hi[2] - b.lo[2] + 1;
   return dim3((n0 + MNL_BX - 1) / MNL_BX, (n1 + MNL_BY - 1) / MNL_BY, n2);
 }
-static bool empty(const Box &b) {
-  for (int k = 0; k < 3; k++)
-    if (b.hi[k] < b.lo[k]) return true;
-  return false;
-}
-static int rc() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-
 static dim3 lin_grid(const BoxList &bl) {
   long long n = bl.start[bl.n];
   return dim3((unsigned)((n + 255) / 256));
 }
 
+// A runtime palette mode (2 palette, 1 f64 chi1inv, anything else none) or flag as a template
+// argument: fn gets a std::integral_constant, whose value (UM(), B()) is a constant expression.
+template <class F>
+static void with_um(int um, F &&fn) {
+  if (um == 2)
+    fn(std::integral_constant<int, 2>{});
+  else if (um == 1)
+    fn(std::integral_constant<int, 1>{});
+  else
+    fn(std::integral_constant<int, 0>{});
+}
+template <class F>
+static void with_bool(bool b, F &&fn) {
+  if (b)
+    fn(std::true_type{});
+  else
+    fn(std::false_type{});
+}
+
 int k_curl(int ft, const Box &in, const BoxList *sh, const DevGrid &g, const DevFields &f,
            const CurlPlan &p, double courant, void *stream, bool fuseup) {
   hipStream_t s = (hipStream_t)stream;
-  BoxList none{};
-  if (!sh) {
-    if (empty(in)) return 0;
-    dim3 blk(MNL_BX, MNL_BY), grd = grid_for(in);
-    if (ft == T_B)
-      curl_kernel<T_B, false, false><<<grd, blk, 0, s>>>(in, none, g, f, p, courant);
-    else
-      curl_kernel<T_D, false, false><<<grd, blk, 0, s>>>(in, none, g, f, p, courant);
-  } else {
-    if (sh->n == 0 || sh->start[sh->n] == 0) return 0;
-    dim3 grd = lin_grid(*sh);
-    grd.y = 3;
-    if (ft == T_B) {
-      if (fuseup)
-        curl_kernel<T_B, true, true><<<grd, 256, 0, s>>>(in, *sh, g, f, p, courant);
-      else
-        curl_kernel<T_B, true, false><<<grd, 256, 0, s>>>(in, *sh, g, f, p, courant);
+  if (sh ? (sh->n == 0 || sh->start[sh->n] == 0) : empty(in)) return 0;
+  with_bool(ft == T_B, [&](auto B) {
+    constexpr int FT = B() ? T_B : T_D;
+    if (!sh) {
+      curl_kernel<FT, false, false><<<grid_for(in), dim3(MNL_BX, MNL_BY), 0, s>>>(
+          in, BoxList{}, g, f, p, courant);
     } else {
-      if (fuseup)
-        curl_kernel<T_D, true, true><<<grd, 256, 0, s>>>(in, *sh, g, f, p, courant);
-      else
-        curl_kernel<T_D, true, false><<<grd, 256, 0, s>>>(in, *sh, g, f, p, courant);
+      dim3 grd = lin_grid(*sh);
+      grd.y = 3;
+      with_bool(fuseup, [&](auto UP) {
+        curl_kernel<FT, true, UP()><<<grd, 256, 0, s>>>(in, *sh, g, f, p, courant);
+      });
     }
-  }
+  });
   return rc();
 }
 
@@ -1424,28 +1105,22 @@ static void launch_e1(const Box &in, const BoxList &bl, const DevGrid &g, const 
 template <bool SHELL>
 static void launch_e(const Box &in, const BoxList &bl, const DevGrid &g, const DevFields &f,
                      const ISrcDev &is, int step, bool fuse, hipStream_t s) {
-  const bool nr = f.nr_enabled != 0, up = f.upnl != 0, isrc = is.n > 0;
-  if (nr) {
-    if (isrc)
-      launch_e1<SHELL, true, false, true, false>(in, bl, g, f, is, step, s);
-    else
-      launch_e1<SHELL, true, false, false, false>(in, bl, g, f, is, step, s);
-  } else if (up) {
-    if (isrc)
-      launch_e1<SHELL, false, true, true, false>(in, bl, g, f, is, step, s);
-    else
-      launch_e1<SHELL, false, true, false, false>(in, bl, g, f, is, step, s);
-  } else if (fuse) {
-    if (isrc)
-      launch_e1<SHELL, false, false, true, true>(in, bl, g, f, is, step, s);
-    else
-      launch_e1<SHELL, false, false, false, true>(in, bl, g, f, is, step, s);
-  } else {
-    if (isrc)
-      launch_e1<SHELL, false, false, true, false>(in, bl, g, f, is, step, s);
-    else
-      launch_e1<SHELL, false, false, false, false>(in, bl, g, f, is, step, s);
-  }
+  // at most one of NR, UP, FUSE: the other combinations are not built
+  auto go = [&](auto NR, auto UP, auto FUSE) {
+    with_bool(is.n > 0, [&](auto ISRC) {
+      launch_e1<SHELL, NR(), UP(), ISRC(), FUSE()>(in, bl, g, f, is, step, s);
+    });
+  };
+  constexpr std::true_type Y{};
+  constexpr std::false_type N{};
+  if (f.nr_enabled != 0)
+    go(Y, N, N);
+  else if (f.upnl != 0)
+    go(N, Y, N);
+  else if (fuse)
+    go(N, N, Y);
+  else
+    go(N, N, N);
 }
 
 int k_update_e(const Box &in, const BoxList *sh, const DevGrid &g, const DevFields &f,
@@ -3381,22 +3056,12 @@ __global__ __launch_bounds__(1024) void fused_tile_kernel(FusedArgs a) {
 
 // the tile kernel for palette mode um (2 palette, 1 f64 chi1inv, 0 none); the diagnostics
 // build when the item clock is on
-void launch_tile(const FusedArgs &t, int um, dim3 grd, hipStream_t s) {
-  const dim3 blk(1024);
-  if (t.clk.rec) {
-    if (um == 2)
-      fused_tile_kernel<2, true><<<grd, blk, 0, s>>>(t);
-    else if (um == 1)
-      fused_tile_kernel<1, true><<<grd, blk, 0, s>>>(t);
-    else
-      fused_tile_kernel<0, true><<<grd, blk, 0, s>>>(t);
-  } else if (um == 2) {
-    fused_tile_kernel<2, false><<<grd, blk, 0, s>>>(t);
-  } else if (um == 1) {
-    fused_tile_kernel<1, false><<<grd, blk, 0, s>>>(t);
-  } else {
-    fused_tile_kernel<0, false><<<grd, blk, 0, s>>>(t);
-  }
+static void launch_tile(const FusedArgs &t, int um, dim3 grd, hipStream_t s) {
+  with_um(um, [&](auto UM) {
+    with_bool(t.clk.rec != nullptr, [&](auto CLK) {
+      fused_tile_kernel<UM(), CLK()><<<grd, dim3(1024), 0, s>>>(t);
+    });
+  });
 }
 
 // The palette word shared by every cell of the box [x0, x1] x [y0, y1] x [z0, z1], or ~0u
@@ -3434,88 +3099,41 @@ __global__ void general_uniform_kernel(FusedArgs a, unsigned *flags) {
   if (threadIdx.x == 0) flags[idx] = w;
 }
 
-// chi1inv palette indices over box F: uidx[i] = idx0 | idx1 << 8 | idx2 << 16,
-// tab[c*256 + idx] == u[c][i] exactly; *bad != 0 if some value is missing.
-__global__ void build_uidx_kernel(unsigned *uidx, const double *u0, const double *u1,
-                                  const double *u2, const double *tab, int n0, int n1, int n2,
-                                  Box F, long long st1, long long st2, int *bad) {
-  const int x = F.lo[0] + blockIdx.x * blockDim.x + threadIdx.x, y = F.lo[1] + blockIdx.y,
-            z = F.lo[2] + blockIdx.z;
-  if (x > F.hi[0]) return;
-  const long long i = x + y * st1 + z * st2;
-  const double *u[3] = {u0, u1, u2};
-  const int n[3] = {n0, n1, n2};
-  unsigned w = 0;
-  for (int c = 0; c < 3; c++) {
-    // exact match on the bit pattern (table sorted by bit pattern on the host)
-    const unsigned long long v = (unsigned long long)__double_as_longlong(u[c][i]);
-    const double *t = tab + 256 * c;
-    int lo = 0, hi = n[c] - 1, hit = -1;
-    while (lo <= hi) {
-      const int mid = (lo + hi) >> 1;
-      const unsigned long long tm = (unsigned long long)__double_as_longlong(t[mid]);
-      if (tm == v) {
-        hit = mid;
-        break;
-      }
-      if (tm < v)
-        lo = mid + 1;
-      else
-        hi = mid - 1;
-    }
-    if (hit < 0) {
-      atomicOr(bad, 1);
-      hit = 0;
-    }
-    w |= (unsigned)hit << (8 * c);
-  }
-  uidx[i] = w;
-}
-
-int k_build_uidx(unsigned *uidx, const double *const u[3], const double *tab, const int n[3],
-                 const Box &F, long long st1, long long st2, int *bad, void *stream) {
-  if (empty(F)) return 0;
-  dim3 grd((F.hi[0] - F.lo[0] + 1 + 255) / 256, F.hi[1] - F.lo[1] + 1, F.hi[2] - F.lo[2] + 1);
-  build_uidx_kernel<<<grd, 256, 0, (hipStream_t)stream>>>(uidx, u[0], u[1], u[2], tab, n[0], n[1],
-                                                          n[2], F, st1, st2, bad);
-  return rc();
-}
-
+// CUs of the current device, asked once per device (256 when the runtime does not say)
 int k_cu_count() {
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-  return pr.multiProcessorCount;
-}
-
-static int fused_grid_blocks(int bpc) {
   static int cus[64] = {0};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256 * bpc;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
   if (!cus[dev]) {
     hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256 * bpc;
+    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
     cus[dev] = pr.multiProcessorCount;
   }
-  return cus[dev] * bpc;
+  return cus[dev];
 }
 
-template <int UM>
-static void launch_general_u(const FusedArgs &g, dim3 gr, dim3 b, hipStream_t s) {
-  if (g.npol == 0)
-    fused_general_kernel<UM, 0><<<gr, b, 0, s>>>(g);
-  else if (g.npol == 1)
-    fused_general_kernel<UM, 1><<<gr, b, 0, s>>>(g);
-  else
-    fused_general_kernel<UM, 2><<<gr, b, 0, s>>>(g);
+// Bookkeeping of a persistent launch over n items of counter line `line`: one workgroup per
+// CU, at most wg_limit (> 0) and n.  Returns the workgroup count, gives the line's value before
+// this launch in cbase and advances the host copy by items + workgroups (every workgroup's
+// last fetch fails once).
+static unsigned persistent_blocks(long long n, int wg_limit, int line, unsigned long long *bases,
+                                  unsigned long long &cbase) {
+  long long nb = k_cu_count();
+  if (wg_limit > 0 && nb > wg_limit) nb = wg_limit;
+  if (nb > n) nb = n;
+  cbase = bases[line];
+  bases[line] += (unsigned long long)n + nb;
+  return (unsigned)nb;
 }
+
+// the general kernel for palette mode um and 0, 1 or more polarizations (POL 2: two and more;
+// the same three-way choice as the palette mode)
 static void launch_general(const FusedArgs &g, int um, dim3 gr, dim3 b, hipStream_t s) {
-  if (um == 2)
-    launch_general_u<2>(g, gr, b, s);
-  else if (um == 1)
-    launch_general_u<1>(g, gr, b, s);
-  else
-    launch_general_u<0>(g, gr, b, s);
+  with_um(um, [&](auto UM) {
+    with_um(g.npol == 0 ? 0 : g.npol == 1 ? 1 : 2, [&](auto POL) {
+      fused_general_kernel<UM(), POL()><<<gr, b, 0, s>>>(g);
+    });
+  });
 }
 
 int k_general_uniform(const FusedArgs &a, unsigned *flags, void *stream) {
@@ -3581,27 +3199,21 @@ int k_fused(const FusedArgs &a, int which, void *stream, unsigned long long *bas
     if (which == 5) ie = a.ntit_e, line = 1;
     if (which == 6) ib = a.ntit_e, line = 2;
     if (ie <= ib) return 0;
-    long long nb = fused_grid_blocks(1);
-    if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
-    if (nb > ie - ib) nb = ie - ib;
     FusedArgs t = a;
-    t.gbeg = ib, t.gend = ie, t.ctr_line = line, t.cbase = bases[line];
-    bases[line] += (unsigned long long)(ie - ib) + nb;
-    launch_tile(t, um, dim3((unsigned)nb), s);
+    t.gbeg = ib, t.gend = ie, t.ctr_line = line;
+    const unsigned nb = persistent_blocks(ie - ib, a.wg_limit, line, bases, t.cbase);
+    launch_tile(t, um, dim3(nb), s);
     return hipPeekAtLastError() == hipSuccess ? 0 : 9;
   }
   // general tiles, item range in a.gitems: [0, ngen); chunk-0 items lead ([0, ngen_e))
   int ib = 0, ie = a.ngen, line = 8;
   if (which == 2) ie = a.ngen_e, line = 10;
   if (which == 3) ib = a.ngen_e;
-  long long cus = fused_grid_blocks(1);
-  if (a.wg_limit > 0 && cus > a.wg_limit) cus = a.wg_limit;
   if (ie > ib) {
     FusedArgs g = a;
-    const unsigned nblk = (unsigned)std::min<long long>(cus, ie - ib);
-    g.gbeg = ib, g.gend = ie, g.ctr_line = line, g.cbase = bases[line];
-    bases[line] += (unsigned long long)(ie - ib) + nblk;
-    launch_general(g, um, dim3(nblk), dim3(64 * GEN_WAVES), s);
+    g.gbeg = ib, g.gend = ie, g.ctr_line = line;
+    const unsigned nb = persistent_blocks(ie - ib, a.wg_limit, line, bases, g.cbase);
+    launch_general(g, um, dim3(nb), dim3(64 * GEN_WAVES), s);
   }
   return hipPeekAtLastError() == hipSuccess ? 0 : 9;
 }
@@ -3612,16 +3224,12 @@ int k_tile_items(const FusedArgs &a, const int *items, const int *geo, const uns
   if (a.nelem * 8 >= (long long)MNL_OOB || !a.ctr || !items || !geo || line < 0 ||
       line >= FUSED_NCTR)
     return 2;
-  long long nb = fused_grid_blocks(1);
-  if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
-  if (nb > n) nb = n;
   FusedArgs t = a;
   t.titems = items, t.tgeo = geo, t.tflag = flags;
-  t.gbeg = 0, t.gend = n, t.ctr_line = line, t.cbase = bases[line];
-  bases[line] += (unsigned long long)n + nb;
+  t.gbeg = 0, t.gend = n, t.ctr_line = line;
+  const unsigned nb = persistent_blocks(n, a.wg_limit, line, bases, t.cbase);
   const int um = a.uidx ? 2 : (a.u[0] ? 1 : 0);
-  hipStream_t s = (hipStream_t)stream;
-  launch_tile(t, um, dim3((unsigned)nb), s);
+  launch_tile(t, um, dim3(nb), (hipStream_t)stream);
   return hipPeekAtLastError() == hipSuccess ? 0 : 9;
 }
 
@@ -4092,38 +3700,20 @@ int k_tb2(const TB2Args &a, void *stream, unsigned long long *bases) {
   if (a.nelem * 8 >= (long long)MNL_OOB || !a.ctr || !a.items || a.ctr_line < 0 ||
       a.ctr_line >= FUSED_NCTR)
     return 2;
-  long long nb = fused_grid_blocks(1);
-  if (a.wg_limit > 0 && nb > a.wg_limit) nb = a.wg_limit;
-  if (nb > a.n) nb = a.n;
   TB2Args t = a;
-  t.cbase = bases[a.ctr_line];
-  bases[a.ctr_line] += (unsigned long long)a.n + nb;
-  const int um = a.uidx ? 2 : (a.u[0] ? 1 : 0);
+  const dim3 grd(persistent_blocks(a.n, a.wg_limit, a.ctr_line, bases, t.cbase));
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grd((unsigned)nb), blk(1024);
   // compact DFT boxes (t.ncmp > 0): the variant with their stores; the diagnostics build
-  // (MNL_ITEM_CLOCK) always has them
-  if (t.clk.rec) {
-    if (um == 2)
-      tb2_kernel<2, true, true><<<grd, blk, 0, s>>>(t);
-    else if (um == 1)
-      tb2_kernel<1, true, true><<<grd, blk, 0, s>>>(t);
+  // (MNL_ITEM_CLOCK) always has them, so CLK without CMP is not built
+  with_um(a.uidx ? 2 : (a.u[0] ? 1 : 0), [&](auto UM) {
+    auto go = [&](auto CLK, auto CMP) {
+      tb2_kernel<UM(), CLK(), CMP()><<<grd, dim3(1024), 0, s>>>(t);
+    };
+    if (t.clk.rec)
+      go(std::true_type{}, std::true_type{});
     else
-      tb2_kernel<0, true, true><<<grd, blk, 0, s>>>(t);
-  } else if (t.ncmp > 0) {
-    if (um == 2)
-      tb2_kernel<2, false, true><<<grd, blk, 0, s>>>(t);
-    else if (um == 1)
-      tb2_kernel<1, false, true><<<grd, blk, 0, s>>>(t);
-    else
-      tb2_kernel<0, false, true><<<grd, blk, 0, s>>>(t);
-  } else if (um == 2) {
-    tb2_kernel<2, false, false><<<grd, blk, 0, s>>>(t);
-  } else if (um == 1) {
-    tb2_kernel<1, false, false><<<grd, blk, 0, s>>>(t);
-  } else {
-    tb2_kernel<0, false, false><<<grd, blk, 0, s>>>(t);
-  }
+      with_bool(t.ncmp > 0, [&](auto CMP) { go(std::false_type{}, CMP); });
+  });
   return hipPeekAtLastError() == hipSuccess ? 0 : 9;
 }
 
@@ -4265,916 +3855,6 @@ __global__ void materialize_e_kernel(Box b, DevGrid g, DevFields f) {
 int k_materialize_e(const Box &F, const DevGrid &g, const DevFields &f, void *stream) {
   if (empty(F)) return 0;
   materialize_e_kernel<<<grid_for(F), dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(F, g, f);
-  return rc();
-}
-
-// ----------------------------------------------------------------- DFT
-// dft_chunk::update_dft (src/dft.cpp:265-300), split in two so that the DFT
-// array is read and written once per KB updates instead of once per update:
-//  * dft_sample_kernel (every DFT step): the field averaged from the Yee points
-//    onto the cell centre exactly as the reference does,
-//    (w*0.25)*(((f0 + f1) + f2) + f3) with the weight product precomputed on the
-//    host, into slot u of a small per-point buffer (E read through the
-//    implicit-E rule in fused mode);
-//  * dft_accum_kernel (every KB updates, and at the end of every step batch):
-//    dft += fr_u * phase_u for u = 0..n-1 in update order -- the reference's
-//    sequential accumulation, same operations in the same order, in registers.
-// The DFT array is blocked by wave, [slot/64][freq][slot%64] complex, so a
-// wave's access to one frequency is one contiguous 1-KB span.
-__global__ void dft_sample_kernel(const int *__restrict__ pj, const double *__restrict__ pw,
-                                  const int *__restrict__ pch, const DftChunkDev *__restrict__ ch,
-                                  double *__restrict__ fr_out, long long npts, DevGrid g,
-                                  DevFields f) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npts) return;
-  if (pj[3 * p] < 0) return;  // another rank's point
-  const DftChunkDev cd = ch[pch[p]];
-  const int c = cd.c, d = c % 3;
-  const bool mag = c >= 3;
-  Pt P;
-  P.idx = 0;
-  for (int e = 0; e < 3; e++) {
-    P.j[e] = pj[3 * p + e];
-    P.idx += (long long)P.j[e] * g.sdir[e];
-  }
-  auto val = [&](const Pt &q) -> double {
-    if (mag) {
-      const bool sep = f.H[d] && (f.hall || pml_at(f, g, d, qcoord(g, q, T_H, d, d)));
-      return sep ? f.H[d][q.idx] : f.B[d][q.idx];
-    }
-    if (e_implicit(f, g, d, q)) {
-      const double dv = f.D[d][q.idx];
-      return f.inveps[d] ? dv * f.inveps[d][q.idx] : dv;
-    }
-    return f.E[d][q.idx];
-  };
-  auto nb = [&](const Pt &q, int e) {
-    Pt r = q;
-    r.j[e] += 1;
-    r.idx += g.sdir[e];
-    return r;
-  };
-  double fr;
-  if (cd.avgmode == 2) {
-    const Pt q1 = nb(P, cd.d1), q2 = nb(P, cd.d2), q3 = nb(q1, cd.d2);
-    fr = pw[p] * (val(P) + val(q1) + val(q2) + val(q3));
-  } else if (cd.avgmode == 1) {
-    fr = pw[p] * (val(P) + val(nb(P, cd.d1)));
-  } else {
-    fr = pw[p] * val(P);
-  }
-  fr_out[p] = fr;
-}
-
-// Sampling plan (built once per fused-mode epoch): per point the linear index of the first
-// of the 1-4 Yee values its centred average reads (the others are +d1, +d2, +d1+d2) and, per
-// value, where it lives (0 stored E, 1 implicit E = D * chi1inv, 2 B (H == B), 3 separate H)
-// -- the per-point table lookups of dft_sample_kernel (PML flags, ownership, fused box) done
-// once, so that the per-step sample is one metadata load and independent value loads.
-// sel: bits 0-1 component direction, 2-3 avgmode, 4 + 2v: kind of value v, 12-13 d1, 14-15
-// d2; 0xFFFF: another rank's point.  The chi1inv of implicit-E values: as the palette bytes of
-// the four values (spal, with uidx / utab: 4 B per point instead of 32) and as doubles (su,
-// the fallback); *bad is set when a palette value is not bitwise the chi1inv array's.
-__global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restrict__ pch,
-                                const DftChunkDev *__restrict__ ch, long long npts, DevGrid g,
-                                DevFields f, const unsigned *__restrict__ uidx,
-                                const double *__restrict__ utab, int *__restrict__ sidx,
-                                unsigned short *__restrict__ ssel, unsigned *__restrict__ spal,
-                                double4 *__restrict__ su, int *__restrict__ bad, Box cb,
-                                int *__restrict__ sci) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npts) return;
-  if (pj[3 * p] < 0) {
-    ssel[p] = 0xFFFF;
-    sidx[p] = 0;
-    spal[p] = 0;
-    su[p] = make_double4(1.0, 1.0, 1.0, 1.0);
-    if (sci) sci[p] = -1;
-    return;
-  }
-  const DftChunkDev cd = ch[pch[p]];
-  const int c = cd.c, d = c % 3;
-  const bool mag = c >= 3;
-  Pt P;
-  P.idx = 0;
-  for (int e = 0; e < 3; e++) {
-    P.j[e] = pj[3 * p + e];
-    P.idx += (long long)P.j[e] * g.sdir[e];
-  }
-  auto kind = [&](const Pt &q) -> unsigned {
-    if (mag) return (f.H[d] && (f.hall || pml_at(f, g, d, qcoord(g, q, T_H, d, d)))) ? 3u : 2u;
-    return e_implicit(f, g, d, q) ? 1u : 0u;
-  };
-  auto nb = [&](const Pt &q, int e) {
-    Pt r = q;
-    r.j[e] += 1;
-    r.idx += g.sdir[e];
-    return r;
-  };
-  Pt q[4] = {P, P, P, P};
-  int nv = 1;
-  if (cd.avgmode == 2) {
-    q[1] = nb(P, cd.d1), q[2] = nb(P, cd.d2), q[3] = nb(q[1], cd.d2);
-    nv = 4;
-  } else if (cd.avgmode == 1) {
-    q[1] = nb(P, cd.d1);
-    nv = 2;
-  }
-  unsigned sel = (unsigned)d | ((unsigned)cd.avgmode << 2) |
-                 ((unsigned)max(cd.d1, 0) << 12) | ((unsigned)max(cd.d2, 0) << 14);
-  double uv[4] = {1.0, 1.0, 1.0, 1.0};  // chi1inv of implicit-E values (x * 1.0 == x otherwise)
-  unsigned pal = 0;
-  bool mism = false;
-  for (int v = 0; v < nv; v++) {
-    const unsigned k = kind(q[v]);
-    sel |= k << (4 + 2 * v);
-    if (k == 1 && f.inveps[d]) {
-      uv[v] = f.inveps[d][q[v].idx];
-      if (uidx) {
-        const unsigned b = (uidx[q[v].idx] >> (8 * d)) & 255u;
-        pal |= b << (8 * v);
-        mism = mism || utab[d * 256 + b] != uv[v];
-      }
-    } else if (k == 1 && uidx) {  // chi1inv == 1: a palette entry equal to 1.0
-      const unsigned b = (uidx[q[v].idx] >> (8 * d)) & 255u;
-      pal |= b << (8 * v);
-      mism = mism || utab[d * 256 + b] != 1.0;
-    }
-  }
-  if (mism) atomicOr(bad, 1);
-  if (sci) {  // compact-box index of the first value if every value lies in the box
-    int c[3], n[3];
-    bool in = true;
-    for (int e = 0; e < 3; e++) {
-      const int ax = g.ax[e] >= 0 ? g.ax[e] : e;
-      c[ax] = P.j[e] - cb.lo[ax];
-      const int top = c[ax] + ((nv > 1 && cd.d1 == e) || (nv > 2 && cd.d2 == e) ? 1 : 0);
-      n[ax] = cb.hi[ax] - cb.lo[ax] + 1;
-      in = in && g.ax[e] >= 0 && c[ax] >= 0 && top < n[ax];
-    }
-    sci[p] = in ? c[0] + n[0] * (c[1] + n[1] * c[2]) : -1;
-  }
-  ssel[p] = (unsigned short)sel;
-  sidx[p] = (int)P.idx;
-  spal[p] = pal;
-  su[p] = make_double4(uv[0], uv[1], uv[2], uv[3]);
-}
-
-struct DftSrc {  // the current buffer set: E, D, B, H per direction
-  const double *E[3], *D[3], *B[3], *H[3];
-};
-
-// implicit E = D * chi1inv with chi1inv from the plan (constant in time; 1.0 where none)
-__device__ __forceinline__ double dft_val(const DftSrc &s, int d, unsigned k, int i, double u) {
-  if (k == 0) return s.E[d][i];
-  if (k == 1) return s.D[d][i] * u;
-  return k == 2 ? s.B[d][i] : s.H[d][i];
-}
-
-// fields::update_dfts' sample of one update (src/dft.cpp:265-300): the reference's centred
-// average (w * 0.25) * (((f0 + f1) + f2) + f3) through the plan, for every flux object due at
-// this step in one launch (DftSampleJobs: the workgroups of job i are blk0[i] ..)
-typedef const DftSampleJobs __attribute__((address_space(4))) KDJ;
-__global__ void __launch_bounds__(256) dft_sample_jobs_kernel(DftSampleJobs J, DftSrc s,
-                                                              const double *__restrict__ utab) {
-  // XCD-aware block order: workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8), so
-  // each XCD takes one contiguous eighth of the points instead; the 2 x 2 averages of
-  // neighbouring rows then meet their shared lines in that XCD's L2
-  const unsigned nb = gridDim.x, xcd = blockIdx.x % 8u, q = nb / 8u, r = nb % 8u;
-  const long long lb = xcd * q + min(xcd, r) + blockIdx.x / 8u;
-  // the job table through the kernarg pointer (wave-uniform index: scalar loads, no copy)
-  KDJ *jt = (KDJ *)__builtin_amdgcn_kernarg_segment_ptr();
-  int ji = 0;
-  for (int i = 1; i < jt->n; i++)
-    if (lb >= jt->j[i].blk0) ji = i;
-  const auto &jb = jt->j[ji];
-  const long long p = (lb - jb.blk0) * 256 + threadIdx.x;
-  if (p >= jb.npts) return;
-  // the point's plan entries, loaded together (one round trip), then the values: compact-box
-  // entries first (all in flight together), field-array loads only for the values the box
-  // does not hold
-  const unsigned sel = jb.ssel[p];
-  const long long i0 = jb.sidx[p];
-  const double w = jb.pw[p];
-  const int ci = jb.cmp ? jb.sci[p] : -1;
-  const unsigned pal = jb.usepal ? jb.spal[p] : 0u;
-  if (sel == 0xFFFFu) return;  // another rank's point
-  const int d = sel & 3, mode = (sel >> 2) & 3, d1 = (sel >> 12) & 3, d2 = (sel >> 14) & 3;
-  const long long s1 = d1 == 0 ? J.sd[0] : (d1 == 1 ? J.sd[1] : J.sd[2]);
-  const long long s2 = d2 == 0 ? J.sd[0] : (d2 == 1 ? J.sd[1] : J.sd[2]);
-  const int nv = mode == 2 ? 4 : (mode == 1 ? 2 : 1);
-  // chi1inv only for implicit-E values (kind 1 in any slot)
-  const bool any1 = ((sel >> 4) & 0x55u & ~((sel >> 5) & 0x55u)) != 0;
-  double u[4] = {1.0, 1.0, 1.0, 1.0};
-  if (any1) {
-    if (jb.usepal) {
-#pragma unroll
-      for (int v = 0; v < 4; v++)
-        if (((sel >> (4 + 2 * v)) & 3) == 1) u[v] = utab[d * 256 + ((pal >> (8 * v)) & 255u)];
-    } else {
-      const double4 uu = ((const double4 *)jb.su)[p];
-      u[0] = uu.x, u[1] = uu.y, u[2] = uu.z, u[3] = uu.w;
-    }
-  }
-  const int c1 = d1 == 0 ? jb.cs[0] : (d1 == 1 ? jb.cs[1] : jb.cs[2]);
-  const int c2 = d2 == 0 ? jb.cs[0] : (d2 == 1 ? jb.cs[1] : jb.cs[2]);
-  const long long li[4] = {i0, i0 + s1, i0 + s2, i0 + s1 + s2};
-  const int cix[4] = {ci, ci + c1, ci + c2, ci + c1 + c2};
-  double val[4];
-  bool got[4];
-#pragma unroll
-  for (int v = 0; v < 4; v++) {  // two-step points from the compact box of this state (dense)
-    const unsigned k = (sel >> (4 + 2 * v)) & 3;
-    const bool use = v < nv && ci >= 0 && (k == 1 || k == 2);
-    val[v] = use ? jb.cmp[(size_t)((k == 1 ? d : 3 + d) * jb.ncell) + cix[v]] : 0.0;
-    got[v] = use;
-  }
-#pragma unroll
-  for (int v = 0; v < 4; v++) {  // the others (and entries no two-step point wrote)
-    const unsigned k = (sel >> (4 + 2 * v)) & 3;
-    if (v >= nv) continue;
-    if (got[v] && (unsigned long long)__double_as_longlong(val[v]) != DFT_CMP_EMPTY)
-      val[v] = k == 1 ? val[v] * u[v] : val[v];
-    else
-      val[v] = dft_val(s, d, k, (int)li[v], u[v]);
-  }
-  double fr;
-  if (mode == 2) {
-    fr = w * (val[0] + val[1] + val[2] + val[3]);
-  } else if (mode == 1) {
-    fr = w * (val[0] + val[1]);
-  } else {
-    fr = w * val[0];
-  }
-  jb.fr[p] = fr;
-}
-
-int k_dft_plan(const int *pj, const int *pch, const DftChunkDev *ch, long long npts,
-               const DevGrid &g, const DevFields &f, const unsigned *uidx, const double *utab,
-               int *sidx, unsigned short *ssel, unsigned *spal, void *su, int *bad,
-               const Box &cbox, int *sci, void *stream) {
-  if (npts <= 0) return 0;
-  dft_plan_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      pj, pch, ch, npts, g, f, uidx, utab, sidx, ssel, spal, (double4 *)su, bad, cbox, sci);
-  return rc();
-}
-
-int k_dft_sample_jobs(const DftSampleJobs &J, const DevGrid &g, const DevFields &f,
-                      const double *utab, void *stream) {
-  if (J.n <= 0 || J.n > DFT_MAXJ || J.nblk <= 0) return 0;
-  if (J.j[0].blk0 != 0) return 2;
-  DftSampleJobs t = J;
-  for (int d = 0; d < 3; d++) t.sd[d] = g.sdir[d];
-  DftSrc s;
-  for (int d = 0; d < 3; d++) s.E[d] = f.E[d], s.D[d] = f.D[d], s.B[d] = f.B[d], s.H[d] = f.H[d];
-  dft_sample_jobs_kernel<<<(unsigned)J.nblk, 256, 0, (hipStream_t)stream>>>(t, s, utab);
-  return rc();
-}
-
-// Accumulation: one thread per point; a tile of DFT_FT frequencies is loaded
-// into registers at once (DFT_FT independent loads in flight), every buffered
-// update is added in order, and the tile is stored back.  When the whole wave
-// belongs to one chunk (the usual case: slots are sorted by component and
-// position) the phases are wave-uniform and come through scalar loads.
-// one tile of FT frequencies at i0: FT independent loads in flight, every
-// buffered update added in order, FT stores
-template <int FT>
-__device__ __forceinline__ void dft_accum_tile(double2 *__restrict__ dp,
-                                               const double2 *__restrict__ php,
-                                               const double *frv, int n, long long rstride,
-                                               int i0) {
-  double2 v[FT];
-#pragma unroll
-  for (int w = 0; w < FT; w++) v[w] = dp[(i0 + w) * 64];
-#pragma unroll
-  for (int u = 0; u < DFT_KB; u++) {
-    if (u < n) {
-#pragma unroll
-      for (int w = 0; w < FT; w++) {
-        const double2 q = php[u * rstride + i0 + w];
-        v[w].x = v[w].x + frv[u] * q.x;
-        v[w].y = v[w].y + frv[u] * q.y;
-      }
-    }
-  }
-#pragma unroll
-  for (int w = 0; w < FT; w++) dp[(i0 + w) * 64] = v[w];
-}
-
-// tiles of DFT_FT frequencies, then the remainder in tiles of 8, 4, 2, 1
-__device__ __forceinline__ void dft_accum_point(double2 *__restrict__ dp,
-                                                const double2 *__restrict__ php,
-                                                const double *frv, int n, long long rstride,
-                                                int nfreq) {
-  int i0 = 0;
-  for (; i0 + DFT_FT <= nfreq; i0 += DFT_FT) dft_accum_tile<DFT_FT>(dp, php, frv, n, rstride, i0);
-  if (nfreq - i0 >= 8) dft_accum_tile<8>(dp, php, frv, n, rstride, i0), i0 += 8;
-  if (nfreq - i0 >= 4) dft_accum_tile<4>(dp, php, frv, n, rstride, i0), i0 += 4;
-  if (nfreq - i0 >= 2) dft_accum_tile<2>(dp, php, frv, n, rstride, i0), i0 += 2;
-  if (nfreq - i0 >= 1) dft_accum_tile<1>(dp, php, frv, n, rstride, i0);
-}
-
-// one tile of FT frequencies at i0 with the phases of the block's chunk staged in LDS
-// (sph[u][DFT_FT], tile-relative column woff + w): broadcast LDS reads instead of a dependent
-// global / scalar load per phase
-template <int FT>
-__device__ __forceinline__ void dft_accum_tile_lds(double2 *__restrict__ dp, const double2 *sph,
-                                                   const double *frv, int n, int i0, int woff) {
-  double2 v[FT];
-#pragma unroll
-  for (int w = 0; w < FT; w++) v[w] = dp[(i0 + woff + w) * 64];
-#pragma unroll
-  for (int u = 0; u < DFT_KB; u++) {
-    if (u < n) {
-#pragma unroll
-      for (int w = 0; w < FT; w++) {
-        const double2 q = sph[u * DFT_FT + woff + w];
-        v[w].x = v[w].x + frv[u] * q.x;
-        v[w].y = v[w].y + frv[u] * q.y;
-      }
-    }
-  }
-#pragma unroll
-  for (int w = 0; w < FT; w++) dp[(i0 + woff + w) * 64] = v[w];
-}
-
-__global__ void __launch_bounds__(256)
-    dft_accum_kernel(const int *__restrict__ pj, const int *__restrict__ pch,
-                     double2 *__restrict__ dft, const double *__restrict__ fr, int n,
-                     const double2 *__restrict__ ph, long long rstride, int nfreq,
-                     long long npts) {
-  __shared__ double2 sph[DFT_KB * DFT_FT];
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = p < npts && pj[3 * p] >= 0;
-  const int k = pch[p < npts ? p : npts - 1];
-  const int kb = pch[(long long)blockIdx.x * blockDim.x];
-  const bool uni = __syncthreads_and(k == kb);  // one chunk (one phase row) for the block
-  double frv[DFT_KB];
-#pragma unroll
-  for (int u = 0; u < DFT_KB; u++) frv[u] = (live && u < n) ? fr[u * npts + p] : 0.0;
-  double2 *__restrict__ dp = dft + (p >> 6) * nfreq * 64 + (p & 63);
-  if (!uni) {
-    if (live) dft_accum_point(dp, ph + (long long)k * nfreq, frv, n, rstride, nfreq);
-    return;
-  }
-  const double2 *php = ph + (long long)kb * nfreq;
-  for (int i0 = 0; i0 < nfreq; i0 += DFT_FT) {  // block-uniform loop
-    const int ft = min(DFT_FT, nfreq - i0);
-    __syncthreads();  // the previous tile's readers are done
-    for (int e = threadIdx.x; e < n * DFT_FT; e += blockDim.x) {
-      const int u = e / DFT_FT, w = e % DFT_FT;
-      if (w < ft) sph[e] = php[u * rstride + i0 + w];
-    }
-    __syncthreads();
-    if (!live) continue;
-    if (ft == DFT_FT) {
-      dft_accum_tile_lds<DFT_FT>(dp, sph, frv, n, i0, 0);
-    } else {  // the last, partial tile in pieces of 8, 4, 2, 1
-      int w0 = 0;
-      if (ft - w0 >= 8) dft_accum_tile_lds<8>(dp, sph, frv, n, i0, w0), w0 += 8;
-      if (ft - w0 >= 4) dft_accum_tile_lds<4>(dp, sph, frv, n, i0, w0), w0 += 4;
-      if (ft - w0 >= 2) dft_accum_tile_lds<2>(dp, sph, frv, n, i0, w0), w0 += 2;
-      if (ft - w0 >= 1) dft_accum_tile_lds<1>(dp, sph, frv, n, i0, w0);
-    }
-  }
-}
-
-int k_dft_sample(const int *pj, const double *pw, const int *pch, const DftChunkDev *ch, double *fr,
-                 long long npts, const DevGrid &g, const DevFields &f, void *stream) {
-  if (npts <= 0) return 0;
-  dft_sample_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      pj, pw, pch, ch, fr, npts, g, f);
-  return rc();
-}
-
-int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, int n,
-                const double *ph, long long rstride, int nfreq, long long npts, void *stream) {
-  if (npts <= 0 || n <= 0) return 0;
-  if (n > DFT_KB || nfreq < 1) return 2;
-  dft_accum_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      pj, pch, (double2 *)dft, fr, n, (const double2 *)ph, rstride, nfreq, npts);
-  return rc();
-}
-
-// ------------------------------------------------- DFT data in list order
-// get / load / scale of the DFT values (save_dft_hdf5 / load_dft_hdf5 / dft_chunk::scale_dft,
-// src/dft.cpp:401-496).  The array is [slot/64][freq][slot%64]; the public order is the
-// reference's list order [list point][freq].  Gather and scatter walk the array in slot order:
-// one wave per block of 64 slots and tile of DFT_DT frequencies, so that every access to the
-// blocked array is one contiguous 1-KB span, and the 64 x DFT_DT tile is transposed through
-// LDS so that the list side moves DFT_DT * 16 B = one whole 128-B line per point.  inv[slot] is
-// the slot's index in the list, or -1 (another list, another rank's point, the padded tail).
-constexpr int DFT_DT = 8;      // frequencies per tile
-constexpr int DFT_DW = 4;      // waves (slot blocks) per workgroup
-constexpr int DFT_DP = 64 + 1; // LDS row pitch in double2
-
-__global__ void __launch_bounds__(64 * DFT_DW)
-    dft_gather_kernel(const double2 *__restrict__ dft, const int *__restrict__ inv,
-                      double2 *__restrict__ out, int nfreq, long long nblk) {
-  __shared__ double2 tile[DFT_DW][DFT_DT][DFT_DP];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long blk = (long long)blockIdx.x * DFT_DW + wv;
-  const int i0 = blockIdx.y * DFT_DT, ft = min(DFT_DT, nfreq - i0);
-  const bool on = blk < nblk;
-  const int k = on ? inv[blk * 64 + lane] : -1;
-  if (on) {
-    const double2 *__restrict__ dp = dft + (blk * nfreq + i0) * 64 + lane;
-#pragma unroll
-    for (int w = 0; w < DFT_DT; w++)
-      if (w < ft) tile[wv][w][lane] = dp[w * 64];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < DFT_DT; it++) {  // 8 lanes per point: its DFT_DT frequencies in a row
-    const int q = it * (64 / DFT_DT) + lane / DFT_DT, w = lane % DFT_DT;
-    const int kq = __shfl(k, q);
-    if (kq >= 0 && w < ft) out[(long long)kq * nfreq + i0 + w] = tile[wv][w][q];
-  }
-}
-
-// the inverse: dft[slot] = sign * in[list point] for the slots of this list
-__global__ void __launch_bounds__(64 * DFT_DW)
-    dft_scatter_kernel(double2 *__restrict__ dft, const int *__restrict__ inv,
-                       const double2 *__restrict__ in, double sign, int nfreq, long long nblk) {
-  __shared__ double2 tile[DFT_DW][DFT_DT][DFT_DP];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long blk = (long long)blockIdx.x * DFT_DW + wv;
-  const int i0 = blockIdx.y * DFT_DT, ft = min(DFT_DT, nfreq - i0);
-  const bool on = blk < nblk;
-  const int k = on ? inv[blk * 64 + lane] : -1;
-#pragma unroll
-  for (int it = 0; it < DFT_DT; it++) {
-    const int q = it * (64 / DFT_DT) + lane / DFT_DT, w = lane % DFT_DT;
-    const int kq = __shfl(k, q);
-    if (kq >= 0 && w < ft) {
-      const double2 v = in[(long long)kq * nfreq + i0 + w];
-      tile[wv][w][q] = make_double2(sign * v.x, sign * v.y);
-    }
-  }
-  __syncthreads();
-  if (k >= 0) {
-    double2 *__restrict__ dp = dft + (blk * nfreq + i0) * 64 + lane;
-#pragma unroll
-    for (int w = 0; w < DFT_DT; w++)
-      if (w < ft) dp[w * 64] = tile[wv][w][lane];
-  }
-}
-
-// dft[i] *= s with the two roundings per product of std::complex<double>::operator*= on finite
-// values (no contraction: -ffp-contract=off)
-__global__ void __launch_bounds__(256)
-    dft_scale_kernel(double2 *__restrict__ dft, double c, double d, long long n) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const double2 v = dft[i];
-    const double ac = v.x * c, bd = v.y * d, ad = v.x * d, bc = v.y * c;
-    dft[i] = make_double2(ac - bd, ad + bc);
-  }
-}
-
-int k_dft_gather(const double *dft, const int *inv, double *out, int nfreq, long long nslots,
-                 void *stream) {
-  const long long nblk = (nslots + 63) / 64;
-  if (nblk <= 0 || nfreq < 1) return 0;
-  const long long gx = (nblk + DFT_DW - 1) / DFT_DW, gy = (nfreq + DFT_DT - 1) / DFT_DT;
-  if (gx > 0x7fffffffLL || gy > 65535) return 2;
-  dft_gather_kernel<<<dim3((unsigned)gx, (unsigned)gy), 64 * DFT_DW, 0, (hipStream_t)stream>>>(
-      (const double2 *)dft, inv, (double2 *)out, nfreq, nblk);
-  return rc();
-}
-
-int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, int nfreq,
-                  long long nslots, void *stream) {
-  const long long nblk = (nslots + 63) / 64;
-  if (nblk <= 0 || nfreq < 1) return 0;
-  const long long gx = (nblk + DFT_DW - 1) / DFT_DW, gy = (nfreq + DFT_DT - 1) / DFT_DT;
-  if (gx > 0x7fffffffLL || gy > 65535) return 2;
-  dft_scatter_kernel<<<dim3((unsigned)gx, (unsigned)gy), 64 * DFT_DW, 0, (hipStream_t)stream>>>(
-      (double2 *)dft, inv, (const double2 *)in, sign, nfreq, nblk);
-  return rc();
-}
-
-int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream) {
-  if (ncomplex <= 0) return 0;
-  const long long nb = std::min<long long>((ncomplex + 255) / 256, 1 << 16);
-  dft_scale_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>((double2 *)dft, re, im, ncomplex);
-  return rc();
-}
-
-// ------------------------------------------------- near-to-far-field transform
-// dft_near2far::farfield_lowlevel (src/near2far.cpp:340-387) for a block of NP far points and
-// a tile of FT frequencies over one workgroup's slot range.  Lanes are slots (the DFT array's
-// [slot/64][freq][slot%64] layout: coalesced 16-byte reads); x - x0, r and rhat are formed once
-// per (slot, far point) and every DFT value once per slot and frequency, so the sincos and the
-// green3d arithmetic dominate.  Each lane keeps its 12 doubles per (far point, frequency) in
-// registers over the whole slot range; one wave reduction and one LDS pass per workgroup at
-// the end.  The sums of one (far point, frequency) never depend on the other members of the
-// block or tile, so a far point's result is the same in every batch.
-__device__ __forceinline__ double n2f_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-template <int FT, int NP>
-__global__ __launch_bounds__(64 * N2F_WAVES) void n2f_farfield_kernel(N2FArgs a) {
-  __shared__ double red[N2F_WAVES][NP * FT * 12];
-  constexpr double pi = 3.141592653589793238462643383276;  // meep::pi
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int f0 = blockIdx.y * FT, p0 = blockIdx.z * NP;
-  const double n = sqrt(a.eps * a.mu), Z = sqrt(a.mu / a.eps);
-  double kk[FT], kinv[FT], ce[FT], cm[FT];
-#pragma unroll
-  for (int w = 0; w < FT; w++) {  // tail tiles repeat the last frequency (not written)
-    const double k = 2 * pi * a.freq[min(f0 + w, a.nfreq - 1)] * n;
-    kk[w] = k;
-    kinv[w] = 1.0 / k;
-    ce[w] = k * n / (4 * pi) / a.eps;
-    cm[w] = k * n / (4 * pi) / a.mu;
-  }
-  double X[NP][3];
-#pragma unroll
-  for (int q = 0; q < NP; q++)  // tail blocks repeat the last far point (not written)
-#pragma unroll
-    for (int d = 0; d < 3; d++) X[q][d] = a.xyz[3 * (long long)min(p0 + q, a.npts - 1) + d];
-  double acc[NP][FT][12];
-#pragma unroll
-  for (int q = 0; q < NP; q++)
-#pragma unroll
-    for (int w = 0; w < FT; w++)
-#pragma unroll
-      for (int j = 0; j < 12; j++) acc[q][w][j] = 0.0;
-  const long long nblk = (a.nslots + 63) >> 6;
-  const long long b0 = (long long)blockIdx.x * a.wg_blocks;
-  const long long b1 = min(b0 + (long long)a.wg_blocks, nblk);
-  const double2 *__restrict__ dft = reinterpret_cast<const double2 *>(a.dft);
-  for (long long b = b0 + wave; b < b1; b += N2F_WAVES) {
-    const long long s = b * 64 + lane;
-    if (s >= a.nslots) continue;  // the padded tail of the last block
-    // the run of this slot: c0 is uniform over long slot runs, so the two sides of the
-    // electric / magnetic choice below are wave-uniform except where a wave straddles two runs
-    int lo = 0, hi = a.nruns - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.runs[mid].first <= s)
-        lo = mid;
-      else
-        hi = mid - 1;
-    }
-    const int c0 = a.runs[lo].c0;
-    const bool elec = c0 < 3;
-    const int dir = c0 % 3;
-    const double px = dir == 0 ? 1.0 : 0.0, py = dir == 1 ? 1.0 : 0.0, pz = dir == 2 ? 1.0 : 0.0;
-    const double zf = elec ? 1.0 / Z : -Z;
-    const double x0 = a.x0[s], y0 = a.x0[a.npad + s], z0 = a.x0[2 * a.npad + s];
-    double rh[NP][3], rcp[NP][3], rinv[NP], rr[NP], pdr[NP];
-#pragma unroll
-    for (int q = 0; q < NP; q++) {
-      const double dx = X[q][0] - x0, dy = X[q][1] - y0, dz = X[q][2] - z0;
-      const double r = sqrt(dx * dx + dy * dy + dz * dz);
-      rr[q] = r;
-      rinv[q] = 1.0 / r;
-      rh[q][0] = dx / r, rh[q][1] = dy / r, rh[q][2] = dz / r;
-      pdr[q] = px * rh[q][0] + py * rh[q][1] + pz * rh[q][2];
-      rcp[q][0] = rh[q][1] * pz - rh[q][2] * py;
-      rcp[q][1] = rh[q][2] * px - rh[q][0] * pz;
-      rcp[q][2] = rh[q][0] * py - rh[q][1] * px;
-    }
-#pragma unroll
-    for (int w = 0; w < FT; w++) {
-      const double2 f = dft[(b * a.nfreq + min(f0 + w, a.nfreq - 1)) * 64 + lane];
-      const double cw = elec ? ce[w] : cm[w];
-#pragma unroll
-      for (int q = 0; q < NP; q++) {
-        double sn, cs;
-        sincos(kk[w] * rr[q] + pi * 0.5, &sn, &cs);
-        const double amp = cw * rinv[q];
-        const double pc = amp * cs, ps = amp * sn;
-        const double er = f.x * pc - f.y * ps, ei = f.x * ps + f.y * pc;  // expfac
-        const double inv = kinv[w] * rinv[q];  // 1 / (k r)
-        const double i2 = -(inv * inv);        // 1 / (i k r)^2
-        const double t1r = 1.0 + i2, t1i = inv;
-        const double t2r = (-1.0 - 3.0 * i2) * pdr[q], t2i = (-3.0 * inv) * pdr[q];
-        const double qr = (er - ei * inv) * zf, qi = (er * inv + ei) * zf;  // expfac * term3
-        double mn[6], cr[6];
-        const double pv[3] = {px, py, pz};
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const double mr = t1r * pv[j] + t2r * rh[q][j], mi = t1i * pv[j] + t2i * rh[q][j];
-          mn[2 * j] = er * mr - ei * mi;
-          mn[2 * j + 1] = er * mi + ei * mr;
-          cr[2 * j] = qr * rcp[q][j];
-          cr[2 * j + 1] = qi * rcp[q][j];
-        }
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-          acc[q][w][j] += elec ? mn[j] : cr[j];
-          acc[q][w][6 + j] += elec ? cr[j] : mn[j];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NP; q++)
-#pragma unroll
-    for (int w = 0; w < FT; w++)
-#pragma unroll
-      for (int j = 0; j < 12; j++) {
-        const double v = n2f_wave_sum(acc[q][w][j]);
-        if (lane == 0) red[wave][(q * FT + w) * 12 + j] = v;
-      }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < NP * FT * 12) {
-    const int q = t / (FT * 12), w = (t / 12) % FT, j = t % 12;
-    if (p0 + q < a.npts && f0 + w < a.nfreq) {
-      double v = red[0][t];
-#pragma unroll
-      for (int k = 1; k < N2F_WAVES; k++) v += red[k][t];
-      a.part[(((long long)blockIdx.x * a.npts + p0 + q) * a.nfreq + f0 + w) * 12 + j] = v;
-    }
-  }
-}
-
-// out[i] = the workgroups' partial sums of element i, added in workgroup order
-__global__ void __launch_bounds__(256)
-    n2f_reduce_kernel(const double *__restrict__ part, double *__restrict__ out, int nwg,
-                      long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double v = 0.0;
-  for (int g = 0; g < nwg; g++) v += part[g * n + i];
-  out[i] = v;
-}
-
-int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream) {
-  if (a.npts <= 0 || nwg <= 0) return 0;
-  if (a.nfreq < 1 || a.nruns < 1 || a.wg_blocks < 1) return 2;
-  const dim3 grd((unsigned)nwg, (unsigned)((a.nfreq + N2F_FT - 1) / N2F_FT),
-                 (unsigned)((a.npts + N2F_NP - 1) / N2F_NP));
-  if (grd.y > 65535 || grd.z > 65535) return 2;
-  n2f_farfield_kernel<N2F_FT, N2F_NP><<<grd, dim3(64 * N2F_WAVES), 0, (hipStream_t)stream>>>(a);
-  return rc();
-}
-
-int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream) {
-  if (n <= 0) return 0;
-  n2f_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(part, out, nwg,
-                                                                                   n);
-  return rc();
-}
-
-int k_fill(double *p, double v, size_t n, void *stream) {
-  if (n == 0) return 0;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  fill_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, v, n);
-  return rc();
-}
-
-static void canon_strides(const DevGrid &g, long long cs[3]) {
-  // canonical whole-cell layout: Z fastest, then Y, then X (src/vec.cpp:482-494)
-  long long nz = g.ax[2] >= 0 ? g.nglob[2] + 1 : 1;
-  long long ny = g.ax[1] >= 0 ? g.nglob[1] + 1 : 1;
-  cs[2] = g.ax[2] >= 0 ? 1 : 0;
-  cs[1] = g.ax[1] >= 0 ? nz : 0;
-  cs[0] = g.ax[0] >= 0 ? nz * ny : 0;
-}
-
-int k_from_canonical(double *dst, const double *src, const DevGrid &g, int comp_type, int comp_dir,
-                     int zlo_glob, void *stream) {
-  (void)comp_type;
-  (void)comp_dir;
-  (void)zlo_glob;
-  long long cs[3];
-  canon_strides(g, cs);
-  dim3 grd((g.N[0] + MNL_BX - 1) / MNL_BX, (g.N[1] + MNL_BY - 1) / MNL_BY, g.N[2]);
-  from_canonical_kernel<<<grd, dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(dst, src, g, cs[0],
-                                                                               cs[1], cs[2]);
-  return rc();
-}
-
-// fields::initialize_field (src/initialize.cpp:135-161): every point of the
-// rank's array (ghost planes included: LOOP_OVER_VOL covers each chunk's whole
-// array) gets += v; then zero_metal (src/boundaries.cpp:304-339) zeroes the owned
-// points on the metallic high wall of each unshifted direction.  alt != null (H
-// after its lazy allocation): the H array holds the value only where H is
-// separate (PML chunk along c, src/update_eh.cpp:204-209), elsewhere H == B.
-__global__ void init_add_kernel(double *dst, double *alt, const double *src, DevGrid g,
-                                DevFields f, int type, int c, long long cs0, long long cs1,
-                                long long cs2) {
-  int i0 = blockIdx.x * MNL_BX + threadIdx.x;
-  int i1 = blockIdx.y * MNL_BY + threadIdx.y;
-  int i2 = blockIdx.z;
-  if (i0 >= g.N[0] || i1 >= g.N[1]) return;
-  int ii[3] = {i0, i1, i2};
-  Pt p;
-  long long cidx = 0;
-  const long long cs[3] = {cs0, cs1, cs2};
-  bool wall = false;
-  for (int d = 0; d < 3; d++) {
-    p.j[d] = g.ax[d] >= 0 ? ii[g.ax[d]] : 0;
-    if (g.ax[d] < 0) continue;
-    cidx += (long long)(p.j[d] + g.off[d]) * cs[d];
-    if (!shift_of(type, c, d) && p.j[d] + g.off[d] == g.nglob[d]) wall = true;
-  }
-  double *t = dst;
-  bool sep = pml_at(f, g, c, qcoord(g, p, type, c, c));
-  if (f.hall && alt && !sep) {  // H-side materials: H separate in this point's chunk?
-    int rz = 0;
-    for (int e = 0; e < 3; e++) rz = rz * 3 + (g.ax[e] >= 0 ? f.zone[e][qcoord(g, p, type, c, e)] : 1);
-    sep = f.hsep_all || ((f.hsep_zone[rz] >> c) & 1);
-  }
-  if (alt && !sep) t = alt;
-  const long long li = (long long)i0 + i1 * g.st[1] + i2 * g.st[2];
-  const double v = wall ? 0.0 : t[li] + src[cidx];
-  t[li] = v;
-  if (f.hall && alt && !sep) dst[li] = v;  // the H copy of an aliasing chunk follows B
-}
-
-// ------------------------------------------------------------- energy
-// fields::field_energy_in_box(c, where) (src/energy_and_flux.cpp:67-83) ->
-// integrate(2, {Ec, Dc} or {Hc, Bc}) on c's own Yee grid (src/integrate.cpp:
-// 46-129): per point fv = 0.25 * (((f + f) + f) + f) of each field (offsets 0
-// on a component grid), term = (fv0 * fv1) * IVEC_LOOP_WEIGHT.  One launch per
-// reference chunk box; every thread accumulates its terms with TwoSum
-// compensation, the workgroup combines (s, c) pairs in LDS and writes one pair.
-__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
-  s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-}
-
-__global__ __launch_bounds__(256) void energy_kernel(const double *A, const double *Asep,
-                                                     const double *Bv, DevGrid g, DevFields f,
-                                                     int type, int c, EBox box, const double *wt,
-                                                     double *partial) {
-  __shared__ double ls[256], lc[256];
-  const long long n0 = box.dn[0], n1 = box.dn[1], n2 = box.dn[2];
-  const long long ntot = n0 * n1 * n2;
-  double s = 0.0, comp = 0.0;
-  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < ntot;
-       q += (long long)gridDim.x * 256) {
-    const long long a0 = q % n0, r = q / n0, a1 = r % n1, a2 = r / n1;
-    const long long ia[3] = {a0, a1, a2};
-    Pt p;
-    long long li = 0;
-    double w[3];
-    for (int d = 0; d < 3; d++) {
-      const int ax = g.ax[d];
-      w[d] = 1.0;
-      p.j[d] = 0;
-      if (ax < 0) continue;
-      p.j[d] = box.dlo[ax] + (int)ia[ax];
-      li += (long long)p.j[d] * g.st[ax];
-      w[d] = wt[box.wofs[ax] + ia[ax]];
-    }
-    // IVEC_LOOP_WEIGHT order: W(yd[2]) * (W(yd[1]) * (dV * W(yd[0])))
-    const double wgt = w[box.yd[2]] * (w[box.yd[1]] * (box.dV0 * w[box.yd[0]]));
-    const double *src = A;
-    if (Asep && (f.hall || pml_at(f, g, c, qcoord(g, p, type, c, c)))) src = Asep;  // H separate here
-    const double x = src[li], y = Bv[li];
-    const double xv = 0.25 * (((x + x) + x) + x), yv = 0.25 * (((y + y) + y) + y);
-    const double t = (xv * yv) * wgt;
-    double ns, e;
-    two_sum(s, t, ns, e);
-    s = ns;
-    comp += e;
-  }
-  ls[threadIdx.x] = s;
-  lc[threadIdx.x] = comp;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if ((int)threadIdx.x < k) {
-      double ns, e;
-      two_sum(ls[threadIdx.x], ls[threadIdx.x + k], ns, e);
-      ls[threadIdx.x] = ns;
-      lc[threadIdx.x] = lc[threadIdx.x] + lc[threadIdx.x + k] + e;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = ls[0];
-    partial[2 * blockIdx.x + 1] = lc[0];
-  }
-}
-
-int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,
-             const DevFields &f, int type, int c, const EBox &box, const double *wt,
-             double *partial, int nblocks, void *stream) {
-  energy_kernel<<<nblocks, 256, 0, (hipStream_t)stream>>>(A, Asep, Bv, g, f, type, c, box, wt,
-                                                          partial);
-  return rc();
-}
-
-// average_with_backup (src/energy_and_flux.cpp:136-144): f = 0.5 * (f + backup)
-__global__ void average_kernel(double *f, const double *bk, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) f[i] = 0.5 * (f[i] + bk[i]);
-}
-
-int k_average(double *f, const double *bk, long long n, void *stream) {
-  if (n <= 0) return 0;
-  average_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(f, bk, n);
-  return rc();
-}
-
-// lazy allocation on the first update_eh (src/update_eh.cpp:204-216): H starts
-// as a copy of B, and the W auxiliary field as a copy of the field it shadows
-__global__ void copy_kernel(double *dst, const double *src, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[i];
-}
-
-int k_copy(double *dst, const double *src, long long n, void *stream) {
-  if (n <= 0) return 0;
-  copy_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(dst, src, n);
-  return rc();
-}
-
-int k_init_add(double *dst, double *alt, const double *src, const DevGrid &g, const DevFields &f,
-               int comp_type, int comp_dir, void *stream) {
-  long long cs[3];
-  canon_strides(g, cs);
-  dim3 grd((g.N[0] + MNL_BX - 1) / MNL_BX, (g.N[1] + MNL_BY - 1) / MNL_BY, g.N[2]);
-  init_add_kernel<<<grd, dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(
-      dst, alt, src, g, f, comp_type, comp_dir, cs[0], cs[1], cs[2]);
-  return rc();
-}
-
-int k_to_box(double *dst, const double *src, const double *hsep, const DevGrid &g, int comp_type,
-             int comp_dir, const DevFields &f, const Box *fusedF, const double *dsrc,
-             const double *usrc, const int blo[3], const int bhi[3], const long long bs[3],
-             void *stream) {
-  (void)fusedF;
-  int l[3] = {0, 0, 0}, n[3] = {1, 1, 1};
-  for (int d = 0; d < 3; d++) {
-    const int a = g.ax[d];
-    if (a < 0) continue;
-    const int lo = std::max(blo[d] - g.off[d], 0), hi = std::min(bhi[d] - g.off[d], g.N[a] - 1);
-    if (hi < lo) return 0;
-    l[a] = lo;
-    n[a] = hi - lo + 1;
-  }
-  int bl[3] = {0, 0, 0};
-  long long bst[3] = {0, 0, 0};
-  for (int d = 0; d < 3; d++)
-    if (g.ax[d] >= 0) bl[d] = blo[d], bst[d] = bs[d];
-  dim3 grd((n[0] + MNL_BX - 1) / MNL_BX, (n[1] + MNL_BY - 1) / MNL_BY, n[2]);
-  to_box_kernel<<<grd, dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(
-      dst, src, hsep, g, f, comp_type, comp_dir, l[0], l[1], l[2], n[0], n[1], bst[0], bst[1],
-      bst[2], bl[0], bl[1], bl[2], fusedF ? 1 : 0, dsrc, usrc);
-  return rc();
-}
-
-int k_to_canonical(double *dst, const double *src, const double *hsep, const DevGrid &g,
-                   int comp_type, int comp_dir, const DevFields &f, const Box *fusedF,
-                   const double *dsrc, const double *usrc, void *stream) {
-  long long cs[3];
-  canon_strides(g, cs);
-  int blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};
-  for (int d = 0; d < 3; d++)
-    if (g.ax[d] >= 0) bhi[d] = g.nglob[d];
-  return k_to_box(dst, src, hsep, g, comp_type, comp_dir, f, fusedF, dsrc, usrc, blo, bhi, cs,
-                  stream);
-}
-
-__global__ void nonzero_box_kernel(const double *a0, const double *a1, const double *a2,
-                                   DevGrid g, int *box) {
-  int i0 = blockIdx.x * MNL_BX + threadIdx.x;
-  int i1 = blockIdx.y * MNL_BY + threadIdx.y;
-  int i2 = blockIdx.z;
-  if (i0 >= g.N[0] || i1 >= g.N[1]) return;
-  const long long i = (long long)i0 + i1 * g.st[1] + i2 * g.st[2];
-  const bool nz = (a0 && a0[i] != 0.0) || (a1 && a1[i] != 0.0) || (a2 && a2[i] != 0.0);
-  if (!nz) return;
-  const int ii[3] = {i0, i1, i2};
-  for (int d = 0; d < 3; d++) {  // per direction, like Pt::j
-    const int j = g.ax[d] >= 0 ? ii[g.ax[d]] : 0;
-    atomicMin(box + d, j);
-    atomicMax(box + 3 + d, j);
-  }
-}
-
-int k_nonzero_box(const double *const a[3], const DevGrid &g, int *box, void *stream) {
-  dim3 grd((g.N[0] + MNL_BX - 1) / MNL_BX, (g.N[1] + MNL_BY - 1) / MNL_BY, g.N[2]);
-  nonzero_box_kernel<<<grd, dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(a[0], a[1], a[2], g,
-                                                                           box);
-  return rc();
-}
-
-int k_avg_chi1inv(const AvgArgs &a, void *stream) {
-  if (a.ntot <= 0) return 0;
-  avg_chi1inv_kernel<<<(unsigned)((a.ntot + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
-  return rc();
-}
-
-int k_box_fill(double *dst, const DevGrid &g, int comp_type, int comp_dir, const double *lo,
-               const double *hi, double value, int invert, double a, const int *io, void *stream) {
-  dim3 grd((g.N[0] + MNL_BX - 1) / MNL_BX, (g.N[1] + MNL_BY - 1) / MNL_BY, g.N[2]);
-  box_fill_kernel<<<grd, dim3(MNL_BX, MNL_BY), 0, (hipStream_t)stream>>>(
-      dst, g, comp_type, comp_dir, lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], value, invert, a,
-      io[0], io[1], io[2]);
   return rc();
 }
 
