@@ -3402,8 +3402,9 @@ __device__ __forceinline__ void tb2_body(const TB2Args &a, const TB2Item it, uns
   const bool own0 = oy && gx >= x0 && gx <= x1, own1 = oy && gx + 1 >= x0 && gx + 1 <= x1;
   // item-uniform: an own range that starts or ends inside a lane's column pair (b64 stores)
   const bool ragged = ((x0 - it.lx) & 1) != 0 || ((x1 - it.lx) & 1) == 0;
-  // the item stores step-n+1 values of some points (rim-bordering faces, DFT / guard box)
-  const bool anymid = (faces & 63) != 0 || it.bx >= 0;
+  // the item stores step-n+1 values of some points (rim-bordering faces, DFT / guard box,
+  // compact DFT box: an item inside L2 on all six sides still owes its monitor the middle step)
+  const bool anymid = (faces & 63) != 0 || it.bx >= 0 || cmi >= 0;
   const unsigned nrec = (unsigned)min(a.nelem * 8, 0xFFFFFFFFLL);
   const gdp D0 = sgpr_ptr(a.Do[0]), D1 = sgpr_ptr(a.Do[1]), D2 = sgpr_ptr(a.Do[2]);
   const gdp B0 = sgpr_ptr(a.Bo[0]), B1 = sgpr_ptr(a.Bo[1]), B2 = sgpr_ptr(a.Bo[2]);

@@ -401,6 +401,27 @@ def test_tb_dft_compact_fallbacks(monkeypatch):
     _same_dft(p5, o5, hs5 + [len(hs5)])
 
 
+def test_tb_dft_compact_interior_items():
+    """Two-step items with no face on the rim (9 columns, 3 planes: most items of L2 have
+    two-step neighbours on all six sides) inside the monitors' compact boxes: an item that
+    stores nothing for the rim or the middle set still stores the middle step for its monitor
+    (seeds 5 and 11 of test_gpu_tb_fuzz.py::test_tb_fuzz_slabs found such items storing only
+    the second step, the middle sample then read a stale middle set).  Per-point DFT values
+    and fluxes bitwise the oracle, with the compact boxes and without."""
+    from scenarios import sc_flux_3d
+    from test_gpu_dft import _same_dft
+    kw = dict(sizes=[9.6, 6.4, 8.0], calls=(None, 12, 12))
+    o, hs = sc_flux_3d(make_oracle, extra=lambda sim: None, **kw)
+    for cmp in (1, 0):
+        def narrow_items(sim):
+            for opt, val in (("tb_ox", 9), ("tb_zchunk", 3), ("dft_cmp", cmp)):
+                sim._fields().set_schedule(opt, val)
+        p, _ = sc_flux_3d(ProductSim, extra=narrow_items, **kw)
+        info = p._fields().tb_info()
+        assert info["active"] and info["tb_width"] == 9 and info["tb_items"] > 300, info
+        _same_dft(p, o, hs)
+
+
 def test_tb_dft_fields():
     """DFT field monitors (whole-cell components, boxes across PML chunks, planes, lines)
     with pairs of steps: bitwise the oracle."""
