@@ -509,8 +509,8 @@ int mnl_fields_dft_load_file(mnl_fields *f, int handle, const char *filename, in
 int mnl_fields_dft_flush(mnl_fields *f);
 /* fields::add_dft_fields(components, ncomp, volume(vmin, vmax), freq, Nfreq,
  * use_centered_grid = !yee_grid, decimation_factor) (src/dft.cpp:889-903; Python
- * Simulation.add_dft_fields, python/simulation.py:2976-3036): E / H components
- * (MNL_EX..MNL_HZ), accumulated on the device with the flux objects' kernels.
+ * Simulation.add_dft_fields, python/simulation.py:2976-3036): any field components
+ * (MNL_EX..MNL_BZ; D and B sample the D and B arrays themselves), accumulated on the device with the flux objects' kernels.
  * *handle is shared with the flux handles (mnl_fields_dft_data, _decimation). */
 int mnl_fields_add_dft_fields(mnl_fields *f, int ncomp, const int *comps, const double vmin[3],
                               const double vmax[3], const double *freqs, int nfreq, int yee_grid,
@@ -524,6 +524,36 @@ int mnl_fields_add_dft_fields(mnl_fields *f, int ncomp, const int *comps, const 
 int mnl_fields_dft_array(mnl_fields *f, int handle, int comp, int num_freq, int *rank,
                          long long dims[3], double *out, long long nout);
 
+/* ---- DFT energy and force monitors (src/dft.cpp:630-790, src/stress.cpp) ----
+ * Objects of up to four chunk lists, accumulated like every other DFT object's; the handle is
+ * shared with the other DFT handles.  `which` of mnl_fields_dft_data / _dft_get / _dft_load /
+ * _dft_points / _dft_list_size and the order of the lists in a mnl_fields_dft_save file:
+ * 0..3 = E, H, D, B for an energy object, 0..2 = offdiag1, offdiag2, diag for a force object.
+ * mnl_fields_dft_array refuses both kinds.
+ *
+ * fields::add_dft_energy (src/dft.cpp:701-727; Python Simulation.add_energy,
+ * python/simulation.py:3357-3400): regions as for mnl_fields_add_dft_flux; direction and
+ * weight are ignored, as in the reference. */
+int mnl_fields_add_dft_energy(mnl_fields *f, int nreg, const double *regions, const double *freqs,
+                              int nfreq, int decimation, int *handle);
+/* fields::add_dft_force (src/stress.cpp:153-191; Python Simulation.add_force,
+ * python/simulation.py:3109-3150): regions as for mnl_fields_add_dft_flux with direction = the
+ * force direction; the normal is that of the region ("cannot determine dft_force normal" for a
+ * region that is not a surface of the cell's dimension). */
+int mnl_fields_add_dft_force(mnl_fields *f, int nreg, const double *regions, const double *freqs,
+                             int nfreq, int decimation, int *handle);
+/* dft_energy::electric / magnetic / total (src/dft.cpp:657-699): which 0 electric, 1 magnetic,
+ * 2 total = electric + magnetic per frequency.  Summed on the device (no atomics: two calls
+ * return the same bits) and over ranks: out[nfreq]. */
+int mnl_fields_dft_energy(mnl_fields *f, int handle, int which, double *out);
+/* dft_force::force (src/stress.cpp:90-114), summed on the device and over ranks: out[nfreq]. */
+int mnl_fields_dft_force(mnl_fields *f, int handle, double *out);
+/* Per point of list `which` of any DFT object, in list order: x, y, z of the DFT point, the
+ * component, and the loop weight as dft_chunk::update_dft applies it (src/dft.cpp:277-282:
+ * after the square root; 1.0 for unweighted lists).  out[5 * n], n >= the list's points. */
+int mnl_fields_dft_points(mnl_fields *f, int handle, int which, double *out, long long n);
+/* Complex values of list `which` (points x nfreq); mnl_fields_dft_size is list 0's. */
+int mnl_fields_dft_list_size(mnl_fields *f, int handle, int which, long long *n);
 /* ---- near-to-far-field monitors (src/near2far.cpp; meep.hpp dft_near2far) ----
  * 3-D, non-periodic.  The DFT is accumulated like every other DFT object's
  * (mnl_fields_dft_data, _dft_size, _dft_decimation, _dft_flush, _dft_array and

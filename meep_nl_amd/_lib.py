@@ -119,6 +119,12 @@ _SIGS = {
     "mnl_fields_dft_array": (c_int, [c_void, c_int, c_int, c_int, iptr,
                                      ctypes.POINTER(ctypes.c_longlong), dptr, ctypes.c_longlong]),
     "mnl_fields_add_dft_near2far": (c_int, [c_void, c_int, dptr, dptr, c_int, c_int, c_int, iptr]),
+    "mnl_fields_add_dft_energy": (c_int, [c_void, c_int, dptr, dptr, c_int, c_int, iptr]),
+    "mnl_fields_add_dft_force": (c_int, [c_void, c_int, dptr, dptr, c_int, c_int, iptr]),
+    "mnl_fields_dft_energy": (c_int, [c_void, c_int, c_int, dptr]),
+    "mnl_fields_dft_force": (c_int, [c_void, c_int, dptr]),
+    "mnl_fields_dft_points": (c_int, [c_void, c_int, c_int, dptr, ctypes.c_longlong]),
+    "mnl_fields_dft_list_size": (c_int, [c_void, c_int, c_int, llptr]),
     "mnl_fields_near2far_farfields": (c_int, [c_void, c_int, ctypes.c_longlong, dptr, dptr]),
     "mnl_fields_near2far_medium": (c_int, [c_void, c_int, dptr, dptr]),
     "mnl_fields_near2far_points": (c_int, [c_void, c_int, dptr, ctypes.c_longlong]),

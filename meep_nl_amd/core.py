@@ -665,11 +665,20 @@ class Fields:
         check(lib().mnl_fields_dft_flux(self.h, h, ptr(out)))
         return out
 
+    def _dft_n(self, h, which):
+        # list 0's size (flux, fields, near2far: every list answers with it, as before);
+        # the list's own for energy and force objects, whose lists differ in length
+        n = ctypes.c_longlong()
+        if h in getattr(self, "_dft_multi", ()):
+            check(lib().mnl_fields_dft_list_size(self.h, h, int(which), ctypes.byref(n)))
+        else:
+            check(lib().mnl_fields_dft_size(self.h, h, ctypes.byref(n)))
+        return n
+
     def dft_data(self, h, which):
         """DFT values of the E (0) or H (1) chunk list, list order (complex); points
         another rank owns read 0."""
-        n = ctypes.c_longlong()
-        check(lib().mnl_fields_dft_size(self.h, h, ctypes.byref(n)))
+        n = self._dft_n(h, which)
         out = np.zeros(2 * n.value, dtype=np.float64)
         check(lib().mnl_fields_dft_data(self.h, h, int(which), ptr(out), n.value))
         return out[0::2] + 1j * out[1::2]
@@ -678,8 +687,7 @@ class Fields:
     def dft_get(self, h, which=0):
         """The values dft_data returns, gathered into list order on the GPU and copied for
         this list only (mnl_fields_dft_get); points another rank owns read 0."""
-        n = ctypes.c_longlong()
-        check(lib().mnl_fields_dft_size(self.h, h, ctypes.byref(n)))
+        n = self._dft_n(h, which)
         out = np.zeros(2 * n.value, dtype=np.float64)
         check(lib().mnl_fields_dft_get(self.h, h, int(which), ptr(out), n.value))
         return out.view(np.complex128)
@@ -749,6 +757,55 @@ class Fields:
         if not rank.value:
             return np.zeros(0, dtype=np.complex128)
         return (out[0:2 * n:2] + 1j * out[1:2 * n:2]).reshape(shape)
+
+    # -- energy and force (fields::add_dft_energy, src/dft.cpp:630-790; add_dft_force,
+    # src/stress.cpp).  Lists: energy 0..3 = E, H, D, B; force 0..2 = offdiag1, offdiag2, diag.
+    def _add_dft_regions(self, fn, regions, freqs, decimation):
+        r = np.ascontiguousarray([list(lo) + list(hi) + [d, w] for lo, hi, d, w in regions],
+                                 dtype=np.float64).ravel()
+        f = np.ascontiguousarray(freqs, dtype=np.float64)
+        h = ctypes.c_int()
+        check(fn(self.h, len(regions), ptr(r), ptr(f), len(f), int(decimation), ctypes.byref(h)))
+        self._dft_nf = getattr(self, "_dft_nf", {})
+        self._dft_nf[h.value] = len(f)
+        self._dft_multi = getattr(self, "_dft_multi", set()) | {h.value}
+        return h.value
+
+    def add_dft_energy(self, regions, freqs, decimation=0):
+        """regions: [(min xyz, max xyz, direction, weight)], direction and weight ignored (as
+        in the reference); returns a handle shared with the other DFT objects."""
+        return self._add_dft_regions(lib().mnl_fields_add_dft_energy, regions, freqs, decimation)
+
+    def add_dft_force(self, regions, freqs, decimation=0):
+        """regions: [(min xyz, max xyz, force direction, weight)]; the normal is the region's."""
+        return self._add_dft_regions(lib().mnl_fields_add_dft_force, regions, freqs, decimation)
+
+    def dft_energy(self, h, which=2):
+        """dft_energy::electric (0) / magnetic (1) / total (2) per frequency, summed on the
+        GPU and over ranks."""
+        out = np.zeros(getattr(self, "_dft_nf", {}).get(h, 1), dtype=np.float64)
+        check(lib().mnl_fields_dft_energy(self.h, h, int(which), ptr(out)))
+        return out
+
+    def dft_force(self, h):
+        """dft_force::force per frequency, summed on the GPU and over ranks."""
+        out = np.zeros(getattr(self, "_dft_nf", {}).get(h, 1), dtype=np.float64)
+        check(lib().mnl_fields_dft_force(self.h, h, ptr(out)))
+        return out
+
+    def dft_list_size(self, h, which=0):
+        """Complex values (points x frequencies) of list `which` of a DFT object."""
+        n = ctypes.c_longlong()
+        check(lib().mnl_fields_dft_list_size(self.h, h, int(which), ctypes.byref(n)))
+        return n.value
+
+    def dft_points(self, h, which=0):
+        """Per point of list `which` (the order of dft_get(h, which)): array (points, 5) of
+        x, y, z, the component and the loop weight as applied (any DFT object)."""
+        npts = self.dft_list_size(h, which) // self._dft_nf[h]
+        out = np.zeros((max(npts, 1), 5), dtype=np.float64)
+        check(lib().mnl_fields_dft_points(self.h, h, int(which), ptr(out), npts))
+        return out[:npts]
 
     # -- near2far (fields::add_dft_near2far / dft_near2far::farfield, src/near2far.cpp)
     def add_dft_near2far(self, regions, freqs, decimation=0, nperiods=1):

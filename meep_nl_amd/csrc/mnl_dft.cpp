@@ -64,10 +64,12 @@ std::vector<std::array<int, 6>> reference_chunks(const mnl_structure &S) {
 // creates, prepended to `list` (their points appended to the flux object's point
 // arrays).  Centered grid, or with yee the component's own grid (loop_in_chunks(...,
 // cgrid = c), src/loop_in_chunks.cpp:350-356: where shifted by yee_shift(Centered) -
-// yee_shift(c), rounded to the dielectric grid, shifted back by iyee_c).
+// yee_shift(c), rounded to the dielectric grid, shifted back by iyee_c).  sqrt_w: the loop
+// weight's square root is applied (sqrt_dV_and_interp_weights, src/dft.cpp:277-280); extra:
+// dft_chunk::extra_weight, kept for the force sum.
 void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const double wmax[3],
              bool incl, cplx stored_weight, double dt_factor, std::vector<DftChunkH> &list,
-             std::vector<double> &pw, bool yee = false) {
+             std::vector<double> &pw, bool yee = false, bool sqrt_w = false, double extra = 1.0) {
   const mnl_structure &S = F->S;
   const DevGrid &g = F->g;
   int is[3] = {0, 0, 0}, ie[3] = {0, 0, 0}, sh[3] = {1, 1, 1};
@@ -151,6 +153,8 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
     dc.dV0 = dV0;
     dc.incl = incl;
     dc.stored = stored_weight;
+    dc.sqrt_w = incl && sqrt_w;
+    dc.extra = extra;
     long ln[3];
     for (int k = 0; k < 3; k++) ln[k] = S.has[yd[k]] ? (iec[yd[k]] - isc[yd[k]]) / 2 + 1 : 1;
     dc.N = size_t(ln[0] * ln[1] * ln[2]);
@@ -177,6 +181,7 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
           for (int k = 0; k < 3; k++)
             if (S.has[yd[k]]) p[yd[k]] = isc[yd[k]] + 2 * int(ii[k]);
           double wt = incl ? (W1(2, i3) * (W1(1, i2) * ((dV0 + 0.0 * i2) * W1(0, i1)))) : 1.0;
+          if (dc.sqrt_w) wt = sqrt(wt);
           w.push_back(wt * fac);
           // this rank owns the centered point if its slab index is in the owned range
           int j[3] = {0, 0, 0};
@@ -204,6 +209,12 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
     made.push_back(dc);
   }
   for (auto &m : made) list.insert(list.begin(), m);
+}
+
+static size_t dft_nchunks(const DftFluxH &o) {
+  size_t n = 0;
+  for (int l = 0; l < o.nlists; l++) n += o.L[l].size();
+  return n;
 }
 
 // updates per accumulation of a new monitor: DFT_KB, or MNL_DFT_BLOCK (1 .. DFT_KB), read when
@@ -245,12 +256,14 @@ int dft_layout(mnl_fields *F, std::unique_ptr<DftFluxH> &o, DftFluxH &ho, std::v
                std::vector<double> &pwH) {
   const int nfreq = o->nfreq;
   // lay out: E points (creation order), then H points; chunks keep their p0
+  // (energy / force objects add every list's points to the object itself: ho is empty)
   const size_t nE = o->h_pj.size() / 3;
-  for (auto &h : o->H) h.p0 += nE;
+  if (!ho.h_pj.empty())
+    for (auto &h : o->H) h.p0 += nE;
   o->h_pj.insert(o->h_pj.end(), ho.h_pj.begin(), ho.h_pj.end());
   pwE.insert(pwE.end(), pwH.begin(), pwH.end());
   o->npts = o->h_pj.size() / 3;
-  // per-point chunk id: chunks numbered E list then H list
+  // per-point chunk id: chunks numbered list by list (E list then H list)
   std::vector<int> pch(o->npts, 0);
   std::vector<DftChunkDev> chd;
   auto lay = [&](const std::vector<DftChunkH> &L) {
@@ -265,13 +278,13 @@ int dft_layout(mnl_fields *F, std::unique_ptr<DftFluxH> &o, DftFluxH &ho, std::v
       chd.push_back(cd);
     }
   };
-  lay(o->E);
-  lay(o->H);
+  for (int l = 0; l < o->nlists; l++) lay(o->L[l]);
+  for (auto &cd : chd) F->dft_samples_d = F->dft_samples_d || cd.c / 3 == T_D;
   // per point and update: 3 indices + chunk id + weight, the averaged field
   // values, the sample written and read back, and 1/kb of a read-modify-write
   // of one complex value per frequency (DESIGN.md "DFT")
-  for (const auto *L : {&o->E, &o->H})
-    for (auto &dc : *L)
+  for (int l = 0; l < o->nlists; l++)
+    for (auto &dc : o->L[l])
       o->bytes += double(dc.N) * (12 + 4 + 8 + 8.0 * (1 << dc.avgmode) + 16 +
                                   (12 + 4 + 32.0 * nfreq) / o->kb);
   // Device slots: the points sorted by component and chunk, then z, y, x (x fastest like
@@ -310,8 +323,11 @@ int dft_layout(mnl_fields *F, std::unique_ptr<DftFluxH> &o, DftFluxH &ho, std::v
     double nc = 1;
     for (int k = 0; k < 3; k++) nc *= o->bbox.hi[k] - o->bbox.lo[k] + 1;
     if (nc * 96 <= double(1u << 30)) o->cmp_cells = (unsigned)nc;
-    for (const auto *L : {&o->E, &o->H})
-      for (auto &dc : *L) o->cmp_mask |= 1u << (dc.c >= 3 ? 3 + dc.c % 3 : dc.c % 3);
+    for (int l = 0; l < o->nlists; l++)  // E and D samples read D_d (bit d), H and B B_d (3 + d)
+      for (auto &dc : o->L[l]) {
+        const bool mag = ctype(dc.c) == T_H || ctype(dc.c) == T_B;
+        o->cmp_mask |= 1u << (mag ? 3 + cdir(dc.c) : cdir(dc.c));
+      }
   }
   if (o->npts) {
     if (dev_alloc(F, &o->d_pj, o->h_pj.size(), false) || dev_alloc(F, &o->d_pch, o->npts, false) ||
@@ -369,9 +385,11 @@ int dft_add_fields(mnl_fields *F, int ncomp, const int *comps, const double wmin
   if (F->src_dirty && build_source_lists(F)) return -1;
   if (ncomp < 1 || nfreq < 1) return fail("add_dft_fields: no components / frequencies");
   for (int k = 0; k < ncomp; k++)
-    if (comps[k] < 0 || comps[k] >= 6) return fail("add_dft_fields: E or H components only");
+    if (comps[k] < 0 || comps[k] >= MNL_NUM_COMPONENTS)
+      return fail("add_dft_fields: not a field component");
   std::unique_ptr<DftFluxH> o(new DftFluxH);
   o->fields = true;
+  o->kind = DFT_FIELDS, o->nlists = 1;
   o->nfreq = nfreq;
   for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]);
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
@@ -383,6 +401,227 @@ int dft_add_fields(mnl_fields *F, int ncomp, const int *comps, const double wmin
   for (int k = 0; k < ncomp; k++)
     dft_add(F, *o, comps[k], wmin, wmax, false, cplx(1.0), dt_factor, o->E, pwE, yee != 0);
   return dft_layout(F, o, ho, pwE, pwH);
+}
+
+// ------------------------------------------------------------------ energy, force
+static std::unique_ptr<DftFluxH> dft_new(mnl_fields *F, int kind, int nlists, const double *R,
+                                         const double *freqs, int nfreq, int decimation) {
+  std::unique_ptr<DftFluxH> o(new DftFluxH);
+  o->kind = kind, o->nlists = nlists;
+  o->nfreq = nfreq;
+  for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]);
+  o->decim = dft_decimation(F, freqs, nfreq, decimation);
+  for (int d = 0; d < 3; d++) o->wmin[d] = R[d], o->wmax[d] = R[3 + d];
+  o->kb = dft_block();
+  return o;
+}
+
+// fields::add_dft_energy (src/dft.cpp:701-727): per region and field direction E_d with the
+// dV and interpolation weights, D_d without, H_d with, B_d without, each prepended to its own
+// list; centred grid, stored weight 1 (the regions' weights do not enter)
+int dft_add_energy(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                   int decimation) {
+  if (F->src_dirty && build_source_lists(F)) return -1;
+  if (nreg < 1 || nfreq < 1) return fail("add_dft_energy: no regions / frequencies");
+  auto o = dft_new(F, DFT_ENERGY, 4, regions, freqs, nfreq, decimation);
+  const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
+  std::vector<double> pw, none;
+  DftFluxH ho;
+  for (int r = 0; r < nreg; r++) {
+    const double *R = regions + 8 * r;
+    for (int d = 0; d < 3; d++) {  // LOOP_OVER_FIELD_DIRECTIONS
+      dft_add(F, *o, MNL_EX + d, R, R + 3, true, cplx(1.0), dt_factor, o->L[0], pw);
+      dft_add(F, *o, MNL_DX + d, R, R + 3, false, cplx(1.0), dt_factor, o->L[2], pw);
+      dft_add(F, *o, MNL_HX + d, R, R + 3, true, cplx(1.0), dt_factor, o->L[1], pw);
+      dft_add(F, *o, MNL_BX + d, R, R + 3, false, cplx(1.0), dt_factor, o->L[3], pw);
+    }
+  }
+  return dft_layout(F, o, ho, pw, none);
+}
+
+// volume::normal_direction (src/vec.cpp): the one direction of the cell in which the region
+// is empty, -1 when there is none or more than one
+static int dft_normal_direction(const mnl_structure &S, const double *R) {
+  if (S.dim == 1) {
+    for (int d = 0; d < 3; d++)
+      if (S.has[d]) return d;
+    return -1;
+  }
+  int nd = -1, nzero = 0;
+  for (int d = 0; d < 3; d++)
+    if (S.has[d] && R[3 + d] - R[d] == 0.0) nd = d, nzero++;
+  return nzero == 1 ? nd : -1;
+}
+
+// fields::add_dft_force (src/stress.cpp:153-191): the stress tensor's terms on a surface with
+// normal nd for the force along fd.  fd != nd: offdiag1 gets E_fd, H_fd (weighted, stored
+// weight = the region's), offdiag2 gets E_nd, H_nd (unweighted), centred grid.  fd == nd: diag
+// gets E_d, H_d of every field direction with square-root weights and the extra weight
+// weight * (+-0.5), on each component's Yee grid.
+int dft_add_force(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                  int decimation) {
+  if (F->src_dirty && build_source_lists(F)) return -1;
+  if (nreg < 1 || nfreq < 1) return fail("add_dft_force: no regions / frequencies");
+  auto o = dft_new(F, DFT_FORCE, 3, regions, freqs, nfreq, decimation);
+  const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
+  std::vector<double> pw, none;
+  DftFluxH ho;
+  for (int r = 0; r < nreg; r++) {
+    const double *R = regions + 8 * r;
+    const int nd = dft_normal_direction(F->S, R);
+    if (nd < 0) return fail("cannot determine dft_force normal");
+    const int fd = int(R[6]);
+    const double wgt = R[7];
+    if (!(R[6] >= 0 && R[6] <= 2)) return fail("NO_DIRECTION dft_force is invalid");
+    for (int d = 0; d < 3; d++) {  // everywhere = the union of the regions
+      o->wmin[d] = std::min(o->wmin[d], R[d]);
+      o->wmax[d] = std::max(o->wmax[d], R[3 + d]);
+    }
+    if (fd != nd) {
+      dft_add(F, *o, MNL_EX + fd, R, R + 3, true, cplx(wgt), dt_factor, o->L[0], pw);
+      dft_add(F, *o, MNL_EX + nd, R, R + 3, false, cplx(1.0), dt_factor, o->L[1], pw);
+      dft_add(F, *o, MNL_HX + fd, R, R + 3, true, cplx(wgt), dt_factor, o->L[0], pw);
+      dft_add(F, *o, MNL_HX + nd, R, R + 3, false, cplx(1.0), dt_factor, o->L[1], pw);
+    } else {
+      for (int d = 0; d < 3; d++) {
+        const double w1 = wgt * (d == fd ? +0.5 : -0.5);
+        dft_add(F, *o, MNL_EX + d, R, R + 3, true, cplx(1.0), dt_factor, o->L[2], pw, true, true, w1);
+        dft_add(F, *o, MNL_HX + d, R, R + 3, true, cplx(1.0), dt_factor, o->L[2], pw, true, true, w1);
+      }
+    }
+  }
+  return dft_layout(F, o, ho, pw, none);
+}
+
+// the runs of lists la and lb zipped (pair_runs, mnl_pair_runs.hpp)
+static long long dft_pair_runs(const DftFluxH &o, int la, int lb, double x,
+                               std::vector<PairRun> &runs, long long total) {
+  std::vector<PairChunk> A, B;
+  for (auto &dc : o.L[la]) A.push_back({dc.p0, dc.N, dc.extra});
+  for (auto &dc : o.L[lb]) B.push_back({dc.p0, dc.N, dc.extra});
+  return pair_runs(A, B, o.h_pj, o.slot, x, runs, total);
+}
+
+static int dft_pair_build(mnl_fields *F, DftFluxH &o, int s) {
+  DftFluxH::PairSum &ps = o.ps[s];
+  if (ps.built) return 0;
+  std::vector<PairRun> runs;
+  long long total = 0;
+  if (o.kind == DFT_ENERGY) {
+    total = dft_pair_runs(o, s, 2 + s, 0.5, runs, 0);  // (E, D) or (H, B)
+  } else {
+    total = dft_pair_runs(o, 0, 1, -1.0, runs, 0);      // stress_sum(offdiag1, offdiag2)
+    total = dft_pair_runs(o, 2, 2, -1.0, runs, total);  // stress_sum(diag, diag)
+  }
+  ps.total = total, ps.nruns = (int)runs.size();
+  // the split into workgroups depends on the object alone
+  const long long per = std::max<long long>(PS_WG_PTS, (total + PS_MAX_WG - 1) / PS_MAX_WG);
+  ps.wg_pts = (int)((per + 255) / 256 * 256);
+  ps.nwg = (int)((total + ps.wg_pts - 1) / ps.wg_pts);
+  if (!runs.empty()) {
+    HIPCHK(hipMalloc(&ps.d_runs, runs.size() * sizeof(PairRun)));
+    HIPCHK(hipMemcpyAsync(ps.d_runs, runs.data(), runs.size() * sizeof(PairRun),
+                          hipMemcpyHostToDevice, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));  // runs leaves scope
+  }
+  ps.built = true;
+  return 0;
+}
+
+// one pair sum on the device, all-reduced like flux(): out[nfreq]
+static int dft_pair_sum(mnl_fields *F, DftFluxH &o, int s, double *out) {
+  const size_t nf = o.nfreq;
+  for (size_t i = 0; i < nf; ++i) out[i] = 0;
+  std::string why;
+  bool ok = true;
+  auto run = [&]() -> int {
+    if (dft_flush(F, o)) return -1;  // the buffered updates first (same stream)
+    if (dft_pair_build(F, o, s)) return -1;
+    const DftFluxH::PairSum &ps = o.ps[s];
+    if (!ps.total) return 0;
+    const size_t need = (size_t)ps.nwg * nf;
+    if (o.ps_part_cap < need) {
+      HIPCHK(hipStreamSynchronize(F->stream));
+      if (o.d_ps_part) (void)hipFree(o.d_ps_part);
+      o.d_ps_part = nullptr, o.ps_part_cap = 0;
+      HIPCHK(hipMalloc(&o.d_ps_part, need * 8));
+      o.ps_part_cap = need;
+    }
+    if (!o.d_ps_out) HIPCHK(hipMalloc(&o.d_ps_out, nf * 8));
+    if (k_dft_pair_sum(o.d_dft, ps.d_runs, ps.nruns, ps.total, ps.wg_pts, ps.nwg, o.nfreq,
+                       (long long)((o.npts + 63) & ~size_t(63)), o.d_ps_part, F->stream))
+      return fail("dft pair sum launch failed");
+    if (k_n2f_reduce(o.d_ps_part, o.d_ps_out, ps.nwg, (long long)nf, F->stream))
+      return fail("dft pair sum reduce launch failed");
+    HIPCHK(hipMemcpyAsync(out, o.d_ps_out, nf * 8, hipMemcpyDeviceToHost, F->stream));
+    HIPCHK(hipStreamSynchronize(F->stream));
+    return 0;
+  };
+  if (run()) ok = false, why = g_err;
+  if (F->nranks > 1) {
+    if (F->comm->agree_ok(ok, F->stream))  // every rank fails together
+      return ok ? fail("dft pair sum: a rank failed") : (g_err = why, -1);
+    for (size_t i0 = 0; i0 < nf; i0 += 64)  // sum_to_all
+      if (timed_allreduce(F, out + i0, (int)std::min<size_t>(64, nf - i0)))
+        return fail("dft pair sum allreduce failed");
+  }
+  if (!ok) return g_err = why, -1;
+  return 0;
+}
+
+// dft_energy::electric / magnetic / total (src/dft.cpp:657-699): which 0, 1, 2
+int dft_energy_values(mnl_fields *F, int h, int which, double *out) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  if (o.kind != DFT_ENERGY) return fail("dft_energy: the handle is not an energy object");
+  if (which < 0 || which > 2)
+    return fail("dft_energy: which must be 0 (electric), 1 (magnetic) or 2 (total)");
+  if (which < 2) return dft_pair_sum(F, o, which, out);
+  std::vector<double> m(o.nfreq);
+  if (dft_pair_sum(F, o, 0, out) || dft_pair_sum(F, o, 1, m.data())) return -1;
+  for (int i = 0; i < o.nfreq; i++) out[i] = out[i] + m[i];
+  return 0;
+}
+
+// dft_force::force (src/stress.cpp:101-114)
+int dft_force_values(mnl_fields *F, int h, double *out) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  DftFluxH &o = *F->dfts[h];
+  if (o.kind != DFT_FORCE) return fail("dft_force: the handle is not a force object");
+  return dft_pair_sum(F, o, 0, out);
+}
+
+// per point of list `which` in list order: x, y, z of the DFT point (IVEC_LOOP_LOC), the
+// component, and the loop weight as update_dft applies it (after the square root; 1.0 for
+// unweighted lists).  Recomputed from the chunks' loops, not stored.
+int dft_points(mnl_fields *F, int h, int which, double *out, long long npoints) {
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  const DftFluxH &o = *F->dfts[h];
+  if (dft_bad_which(o, which)) return fail("dft_points: no such list");
+  const mnl_structure &S = F->S;
+  const int yd[3] = {S.dim == 2 ? 2 : 0, S.dim == 2 ? 0 : 1, S.dim == 2 ? 1 : 2};
+  long long k = 0;
+  for (auto &dc : o.L[which]) {
+    int n[3];
+    for (int q = 0; q < 3; q++) n[q] = S.has[yd[q]] ? (dc.ie[yd[q]] - dc.is[yd[q]]) / 2 + 1 : 1;
+    for (int i1 = 0; i1 < n[0]; i1++)
+      for (int i2 = 0; i2 < n[1]; i2++)
+        for (int i3 = 0; i3 < n[2]; i3++, k++) {
+          if (k >= npoints) return fail("dft_points: buffer too small");
+          const int ii[3] = {i1, i2, i3};
+          double wl[3];
+          for (int q = 0; q < 3; q++) {
+            const int d = yd[q];
+            wl[q] = loop_w1(dc.s0[d], dc.s1[d], dc.e0[d], dc.e1[d], ii[q], n[q]);
+            out[5 * k + d] = S.has[d] ? (dc.is[d] + 2 * ii[q]) * (0.5 * (1.0 / S.a)) : 0.0;
+          }
+          double w = dc.incl ? wl[2] * (wl[1] * ((dc.dV0 + 0.0 * i2) * wl[0])) : 1.0;
+          if (dc.sqrt_w) w = sqrt(w);
+          out[5 * k + 3] = dc.c;
+          out[5 * k + 4] = w;
+        }
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------ near2far
@@ -432,6 +671,7 @@ int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const doubl
   std::unique_ptr<DftFluxH> o(new DftFluxH);
   o->fields = true;  // chunks in E only
   o->n2f = true;
+  o->kind = DFT_N2F, o->nlists = 1;
   o->nfreq = nfreq;
   for (int i = 0; i < nfreq; i++) o->omega.push_back(2 * pi * freqs[i]), o->freq.push_back(freqs[i]);
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
@@ -610,7 +850,7 @@ int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, doubl
 int dft_prepare(mnl_fields *F, long long t0, int ns) {
   for (auto &op : F->dfts) {
     DftFluxH &o = *op;
-    const size_t nch = o.E.size() + o.H.size();
+    const size_t nch = dft_nchunks(o);
     const size_t rowlen = 2 * nch * (size_t)o.nfreq;
     std::vector<double> ph;
     ph.reserve(((size_t)o.nbuf + ns) * rowlen);
@@ -639,7 +879,7 @@ int dft_prepare(mnl_fields *F, long long t0, int ns) {
       };
       auto add = [&](const std::vector<DftChunkH> &L) {
         for (auto &dc : L) {
-          const bool isH = ctype(dc.c) == T_H;
+          const bool isH = ctype(dc.c) == T_H || ctype(dc.c) == T_B;  // is_H_or_B: t - dt/2
           size_t from = SIZE_MAX;
           for (auto &d : done)
             if (d.first.first == isH && same(d.first.second, dc.scale)) from = d.second;
@@ -657,8 +897,7 @@ int dft_prepare(mnl_fields *F, long long t0, int ns) {
           }
         }
       };
-      add(o.E);
-      add(o.H);
+      for (int l = 0; l < o.nlists; l++) add(o.L[l]);
     }
     if (ph.empty()) {
       o.ph_host.clear();
@@ -681,7 +920,7 @@ int dft_prepare(mnl_fields *F, long long t0, int ns) {
 // accumulate the buffered updates of one flux object
 int dft_flush(mnl_fields *F, DftFluxH &o) {
   if (!o.nbuf) return 0;
-  const size_t nch = o.E.size() + o.H.size();
+  const size_t nch = dft_nchunks(o);
   const long long rstride = (long long)(nch * o.nfreq);
   if (k_dft_accum(o.d_pj, o.d_pch, o.d_dft, o.d_fr, o.nbuf,
                   o.d_ph + 2 * (size_t)(o.row - o.nbuf) * rstride, rstride, o.nfreq,
@@ -735,7 +974,7 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
         if (k_dft_plan(o.d_pj, o.d_pch, o.d_ch, (long long)o.npts, F->g, F->f,
                        pal ? F->d_uidx : nullptr, pal ? F->d_utab : nullptr, o.d_sidx, o.d_ssel,
                        o.d_spal, o.d_su, o.d_bad, o.bbox, o.cmp_cells ? o.d_sci : nullptr,
-                       F->stream))
+                       F->pal_one, F->stream))
           return fail("dft plan launch failed");
         int bad = 1;
         if (pal) {  // once per plan: are the palette bytes exact for every implicit value?
@@ -827,6 +1066,8 @@ int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long di
               long long nout) {
   if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
   DftFluxH &o = *F->dfts[h];
+  if (o.kind == DFT_ENERGY || o.kind == DFT_FORCE)
+    return fail("get_dft_array: not available for energy and force objects in this build");
   if (dft_flush(F, o)) return -1;  // the buffered updates first
   if (num_freq < 0 || num_freq > o.nfreq - 1)
     return fail(("process_dft_component: frequency index " + std::to_string(num_freq) +
@@ -931,9 +1172,21 @@ int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long di
 // ------------------------------------------------------------------ DFT data
 // get / load / scale of the accumulated values in list order, replacing
 // save_dft_hdf5 / load_dft_hdf5 (src/dft.cpp:444-496) and dft_chunk::scale_dft (401-405).
+// a list of the object: flux, fields and near2far objects answer for E and H as before (an
+// absent H list is empty), energy objects have 0..3 = E, H, D, B, force objects 0..2 =
+// offdiag1, offdiag2, diag
+bool dft_bad_which(const DftFluxH &o, int which) {
+  return which < 0 || which >= std::max(2, o.nlists);
+}
+const char *dft_list_name(const DftFluxH &o, int which) {
+  static const char *const en[4] = {"E", "H", "D", "B"};
+  static const char *const fo[4] = {"offdiag1", "offdiag2", "diag", ""};
+  return (o.kind == DFT_FORCE ? fo : en)[which & 3];
+}
+
 size_t dft_list_points(const DftFluxH &o, int which) {
   size_t n = 0;
-  for (auto &dc : which ? o.H : o.E) n += dc.N;
+  for (auto &dc : o.L[which]) n += dc.N;
   return n;
 }
 
@@ -944,7 +1197,7 @@ static int dft_list_ready(mnl_fields *F, DftFluxH &o, int which) {
   if (!o.d_inv[which] && npad) {
     std::vector<int> inv(npad, -1);
     int k = 0;
-    for (auto &dc : which ? o.H : o.E)
+    for (auto &dc : o.L[which])
       for (size_t p = dc.p0; p < dc.p0 + dc.N; p++, k++)
         if (o.h_pj[3 * p] >= 0) inv[o.slot[p]] = k;
     HIPCHK(hipMalloc(&o.d_inv[which], npad * 4));
@@ -987,8 +1240,8 @@ static int dft_io_timed(mnl_fields *F, int id, double bytes, Fn launch) {
 
 int dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
   if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
-  if (which != 0 && which != 1) return fail("dft_get: which must be 0 (E) or 1 (H)");
   DftFluxH &o = *F->dfts[h];
+  if (dft_bad_which(o, which)) return fail("dft_get: which must be 0 (E) or 1 (H)");
   const size_t nl = dft_list_points(o, which) * (size_t)o.nfreq;  // complex values
   if (n < 0 || (size_t)n < nl) return fail("dft buffer too small");
   if (dft_flush(F, o)) return -1;  // the buffered updates first (same stream)
@@ -1008,14 +1261,14 @@ int dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
 
 int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign) {
   if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
-  if (which != 0 && which != 1) return fail("dft_load: which must be 0 (E) or 1 (H)");
   if (sign != 1 && sign != -1) return fail("dft_load: sign must be 1 or -1");
   DftFluxH &o = *F->dfts[h];
+  if (dft_bad_which(o, which)) return fail("dft_load: which must be 0 (E) or 1 (H)");
   const size_t nl = dft_list_points(o, which) * (size_t)o.nfreq;
   if (n < 0 || (size_t)n != nl) {
     char b[160];  // load_dft_hdf5 (src/dft.cpp:482-484), sizes in doubles as there
     snprintf(b, sizeof b, "incorrect dataset size (%lld vs. %lld) in load_dft %d:%s",
-             (long long)(2 * n), (long long)(2 * nl), h, which ? "H" : "E");
+             (long long)(2 * n), (long long)(2 * nl), h, dft_list_name(o, which));
     return fail(b);
   }
   // the updates sampled before the load belong to the values it replaces: accumulate them

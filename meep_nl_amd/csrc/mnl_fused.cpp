@@ -469,6 +469,10 @@ static int build_palette(mnl_fields *F) {
     int k = 0;
     for (uint64_t u : cand) memcpy(&tab[256 * c + k++], &u, 8);  // ascending bit patterns
   }
+  F->pal_one = 0;  // the entry of 1.0 (always a candidate): what a DFT sample of raw D multiplies by
+  for (int c = 0; c < 3; c++)
+    for (int k = 0; k < n[c]; k++)
+      if (tab[256 * c + k] == 1.0) F->pal_one |= (unsigned)k << (8 * c);
   unsigned *uidx = nullptr;
   double *utab;
   int *bad;

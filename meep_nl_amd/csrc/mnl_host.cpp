@@ -743,7 +743,8 @@ int mnl_fields_dft_data(mnl_fields *F, int h, int which, double *out, long long 
     HIPCHK(hipMemcpy(v.data(), o.d_dft, v.size() * 8, hipMemcpyDeviceToHost));
   }
   long long k = 0;
-  for (auto &dc : which ? o.H : o.E)
+  if (dft_bad_which(o, which)) return fail("dft_data: no such list");
+  for (auto &dc : o.L[which])
     for (size_t p = 0; p < dc.N; p++)
       for (size_t i = 0; i < nf; i++) {
         if (k + 2 > 2 * n) return fail("dft buffer too small");
@@ -823,6 +824,54 @@ int mnl_fields_near2far_medium(mnl_fields *F, int h, double *eps, double *mu) {
 int mnl_fields_near2far_points(mnl_fields *F, int h, double *out, long long npoints) {
   if (!F || !out) return fail("null argument");
   return n2f_points(F, h, out, npoints);
+}
+
+int mnl_fields_add_dft_energy(mnl_fields *F, int nreg, const double *regions, const double *freqs,
+                              int nfreq, int decimation, int *handle) {
+  if (!F || !regions || !freqs || !handle) return fail("null argument");
+  if (decimation < 0) return fail("decimation must be >= 0");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  const int h = dft_add_energy(F, nreg, regions, freqs, nfreq, decimation);
+  if (h < 0) return -1;
+  *handle = h;
+  return 0;
+}
+
+int mnl_fields_add_dft_force(mnl_fields *F, int nreg, const double *regions, const double *freqs,
+                             int nfreq, int decimation, int *handle) {
+  if (!F || !regions || !freqs || !handle) return fail("null argument");
+  if (decimation < 0) return fail("decimation must be >= 0");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  const int h = dft_add_force(F, nreg, regions, freqs, nfreq, decimation);
+  if (h < 0) return -1;
+  *handle = h;
+  return 0;
+}
+
+int mnl_fields_dft_energy(mnl_fields *F, int h, int which, double *out) {
+  if (!F || !out) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_energy_values(F, h, which, out);
+}
+
+int mnl_fields_dft_force(mnl_fields *F, int h, double *out) {
+  if (!F || !out) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_force_values(F, h, out);
+}
+
+int mnl_fields_dft_points(mnl_fields *F, int h, int which, double *out, long long n) {
+  if (!F || (n > 0 && !out)) return fail("null argument");
+  return dft_points(F, h, which, out, n);
+}
+
+int mnl_fields_dft_list_size(mnl_fields *F, int h, int which, long long *n) {
+  if (!F || !n) return fail("null argument");
+  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  const DftFluxH &o = *F->dfts[h];
+  if (dft_bad_which(o, which)) return fail("dft_list_size: no such list");
+  *n = (long long)dft_list_points(o, which) * o.nfreq;
+  return 0;
 }
 
 int mnl_fields_traffic_model(mnl_fields *F, double *bpc, double *cells) {

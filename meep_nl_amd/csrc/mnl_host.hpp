@@ -205,14 +205,23 @@ struct DftChunkH {
   bool incl;
   cplx stored;
   int c0 = -1;       // near2far: the equivalent current's component (dft_chunk::vc)
+  bool sqrt_w = false;  // sqrt_dV_and_interp_weights: the loop weight's square root is applied
+  double extra = 1.0;   // dft_chunk::extra_weight (used by the force sum only)
 };
+enum { DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4 };
+constexpr int DFT_MAXLISTS = 4;
 struct DftFluxH {
   std::vector<double> omega;
   int nfreq = 0, decim = 1;
   bool fields = false;                // dft_fields (add_dft_fields): chunks in E only
   double wmin[3] = {0, 0, 0}, wmax[3] = {0, 0, 0};  // `where` (get_dft_array's collapse)
-  std::vector<DftChunkH> E, H;        // list order (next_in_dft)
-  size_t npts = 0;                    // E points, then H points
+  // up to four chunk lists in list order (next_in_dft).  flux: E, H; fields / near2far: one
+  // list; energy: E, H, D, B; force: offdiag1, offdiag2, diag
+  int kind = DFT_FLUX;
+  int nlists = 2;
+  std::vector<DftChunkH> L[DFT_MAXLISTS];
+  std::vector<DftChunkH> &E = L[0], &H = L[1];
+  size_t npts = 0;                    // E points, then H points (energy / force: call order)
   std::vector<int> h_pj;              // 3 local indices per point (-1: not this rank's)
   Box bbox{};                         // this rank's points, +1 along every axis (dft_layout;
                                       // empty: lo > hi)
@@ -260,11 +269,25 @@ struct DftFluxH {
   size_t n2f_part_cap = 0, n2f_pts_cap = 0;
   // data in list order: per list the slot -> list index map (-1: not in
   // the list or not this rank's; built at first use) and a device buffer [list point][freq]
-  int *d_inv[2] = {nullptr, nullptr};
+  int *d_inv[DFT_MAXLISTS] = {nullptr, nullptr, nullptr, nullptr};
   double *d_list = nullptr;
   size_t list_cap = 0;                // doubles
+  // pair sums (energy / force): per sum the runs of paired slots, the
+  // fixed split into workgroups, the partial sums [workgroup][freq] and the result
+  struct PairSum {
+    PairRun *d_runs = nullptr;
+    int nruns = 0, nwg = 0, wg_pts = 0;
+    long long total = 0;
+    bool built = false;
+  } ps[2];
+  double *d_ps_part = nullptr, *d_ps_out = nullptr;
+  size_t ps_part_cap = 0;
+  DftFluxH() = default;
+  DftFluxH(const DftFluxH &) = delete;
   ~DftFluxH() {
-    for (void *p : {(void *)d_inv[0], (void *)d_inv[1], (void *)d_list, (void *)d_n2f_part,
+    for (void *p : {(void *)d_inv[0], (void *)d_inv[1], (void *)d_inv[2], (void *)d_inv[3],
+                    (void *)ps[0].d_runs, (void *)ps[1].d_runs, (void *)d_ps_part,
+                    (void *)d_ps_out, (void *)d_list, (void *)d_n2f_part,
                     (void *)d_n2f_xyz, (void *)d_n2f_out, (void *)d_ph, (void *)d_sidx,
                     (void *)d_ssel, (void *)d_spal, d_su, (void *)d_bad, (void *)d_cmp,
                     (void *)d_sci})
@@ -363,6 +386,7 @@ struct mnl_fields {
   bool dsrc_in_shell = false;  // a D source point lies outside the interior box
   bool any_srcB = false, any_isrc = false;  // anywhere in the cell (all ranks agree)
   bool any_dsrc_w = false;  // a D current source on a W-form (PML-along-E) point
+  unsigned pal_one = 0;        // per direction (byte d) the palette entry that is bitwise 1.0
   unsigned *d_uidx = nullptr;  // chi1inv palette indices over fusedG (null: f64 chi1inv)
   double *d_utab = nullptr;    // 3 x 256 palette values
   unsigned long long uflag_sig = 0;  // geometry the flags were built for
@@ -487,6 +511,7 @@ struct mnl_fields {
   double *d_scratch = nullptr;  // canonical-size staging buffer
   size_t scratch_cap = 0;
   std::vector<std::unique_ptr<DftFluxH>> dfts;  // DFT flux objects (add_dft_flux order)
+  bool dft_samples_d = false;  // a monitor samples a D component (its low ghost: exchange 3)
 
   ~mnl_fields() {
     if (device >= 0) hipSetDevice(device);
@@ -764,9 +789,18 @@ long long dft_plan_key(const mnl_fields *F);
 int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1);
 bool dft_due(const mnl_fields *F, long long t);
 int dft_flux_values(mnl_fields *F, int h, double *out);
+int dft_add_energy(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                   int decimation);
+int dft_add_force(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
+                  int decimation);
+int dft_energy_values(mnl_fields *F, int h, int which, double *out);
+int dft_force_values(mnl_fields *F, int h, double *out);
+int dft_points(mnl_fields *F, int h, int which, double *out, long long npoints);
 MNL_HIDDEN int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long dims[3],
                          double *out, long long nout);
 size_t dft_list_points(const DftFluxH &o, int which);
+bool dft_bad_which(const DftFluxH &o, int which);
+const char *dft_list_name(const DftFluxH &o, int which);
 int dft_get(mnl_fields *F, int h, int which, double *out, long long n);
 int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign);
 int dft_scale(mnl_fields *F, int h, double re, double im);

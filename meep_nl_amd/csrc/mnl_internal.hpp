@@ -13,6 +13,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "mnl_pair_runs.hpp"
+
 namespace mnl {
 
 constexpr int MAX_POL = 4;    // Lorentzian susceptibilities per structure
@@ -194,7 +196,7 @@ struct ISrcDev {             // integrated sources, read by the E kernel
 // component, how many Yee points are averaged onto the cell centre and along
 // which directions (grid_volume::yee2cent_offsets, src/vec.cpp:333-344).
 struct DftChunkDev {
-  int c;        // MNL component (E or H)
+  int c;        // MNL component (E, H, D or B)
   int avgmode;  // 0, 1 (d1) or 2 (d1, d2)
   int d1, d2;
 };
@@ -492,6 +494,15 @@ struct N2FArgs {
 // SIMD beat 4x2, 2x4 at 1 wave and 1x2 at 3 waves)
 constexpr int N2F_FT = 2, N2F_NP = 2;
 
+// Pair sums of the energy and force monitors: sum over runs of paired
+// slots of x * real(a * conj(b)) per frequency.  k_dft_pair_sum writes the workgroups' partial
+// sums part[wg][freq]; k_n2f_reduce adds them in workgroup order.
+constexpr int PS_WAVES = 4;        // waves per workgroup
+constexpr int PS_FT = 4;           // frequencies per workgroup (grid y)
+constexpr int PS_MAX_WG = 1024;    // workgroups along x per sum at most
+constexpr int PS_WG_PTS = 4096;    // pair points per workgroup at least (a multiple of 256)
+// PairRun: mnl_pair_runs.hpp
+
 // =============================================================== launchers
 // Host-side launchers of the kernels, one heading per kernel file.  Each but k_cu_count
 // returns 0, or a non-zero code when an argument is bad or the launch failed.
@@ -576,7 +587,7 @@ int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, in
 int k_dft_plan(const int *pj, const int *pch, const DftChunkDev *ch, long long npts,
                const DevGrid &g, const DevFields &f, const unsigned *uidx, const double *utab,
                int *sidx, unsigned short *ssel, unsigned *spal, void *su, int *bad,
-               const Box &cbox, int *sci, void *stream);
+               const Box &cbox, int *sci, unsigned pal_one, void *stream);
 int k_dft_sample_jobs(const DftSampleJobs &J, const DevGrid &g, const DevFields &f,
                       const double *utab, void *stream);
 // DFT data in list order: inv[slot] = index in the list or -1, for
@@ -588,6 +599,8 @@ int k_dft_scatter(double *dft, const int *inv, const double *in, double sign, in
 int k_dft_scale(double *dft, double re, double im, long long ncomplex, void *stream);
 int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream);
 int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream);
+int k_dft_pair_sum(const double *dft, const PairRun *runs, int nruns, long long total, int wg_pts,
+                   int nwg, int nfreq, long long npad, double *part, void *stream);
 
 // ---- mnl_kernels_io.hip: what mnl_io.cpp and the ABI's getters launch
 int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,

@@ -156,10 +156,17 @@ int fields_load(mnl_fields *F, const char *path) {
 // owner, so the sum is exact); every rank reads the whole file and keeps its own points.
 static constexpr char DD_MAGIC[8] = {'M', 'N', 'L', 'D', 'F', 'T', '0', '1'};
 
+// the lists a file holds: E and H of a flux object (E alone when it has no H chunk, as for
+// fields and near2far objects), every list of an energy or force object
+static int dft_file_lists(const DftFluxH &o) {
+  if (o.kind == DFT_ENERGY || o.kind == DFT_FORCE) return o.nlists;
+  return o.H.empty() ? 1 : 2;
+}
+
 int dft_save(mnl_fields *F, int h, const char *path) {
   if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
   DftFluxH &o = *F->dfts[h];
-  const int nlists = o.H.empty() ? 1 : 2;
+  const int nlists = dft_file_lists(o);
   std::vector<std::vector<double>> data(nlists);
   bool ok = true;
   std::string why;
@@ -214,10 +221,10 @@ int dft_load_file(mnl_fields *F, int h, const char *path, int sign) {
   int32_t hd[2];
   if (fread(magic, 8, 1, fp) != 1 || memcmp(magic, DD_MAGIC, 8) || fread(hd, sizeof hd, 1, fp) != 1)
     return fail(std::string("not a dft data file: ") + path);
-  const int nlists = o.H.empty() ? 1 : 2;
+  const int nlists = dft_file_lists(o);
   if (hd[0] != nlists || hd[1] < 1) return fail("dft file holds a different kind of dft object");
   std::vector<double> fr(hd[1]);  // read, not compared value for value (as the reference)
-  uint64_t np[2] = {0, 0};
+  uint64_t np[DFT_MAXLISTS] = {0, 0, 0, 0};
   if (fread(fr.data(), 8, fr.size(), fp) != fr.size() || fread(np, 8, nlists, fp) != (size_t)nlists)
     return fail("dft file: read error (truncated file)");
   for (int l = 0; l < nlists; l++) {
@@ -226,7 +233,7 @@ int dft_load_file(mnl_fields *F, int h, const char *path, int sign) {
     if (file_n != n) {
       char b[200];
       snprintf(b, sizeof b, "incorrect dataset size (%lld vs. %lld) in load_dft %s:%s",
-               (long long)file_n, (long long)n, path, l ? "H" : "E");
+               (long long)file_n, (long long)n, path, dft_list_name(o, l));
       return fail(b);
     }
   }

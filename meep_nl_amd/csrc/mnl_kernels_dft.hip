@@ -1,6 +1,7 @@
 // mnl_kernels_dft.hip -- gfx950 kernels of the DFT monitors (mnl_dft.cpp): the sampler, the
-// sampling plan, the accumulators, gather / scatter / scale of DFT data in list order, and the
-// near-to-far-field transform, with their launchers.
+// sampling plan, the accumulators, gather / scatter / scale of DFT data in list order, the
+// near-to-far-field transform and the pair sums of the energy and force monitors, with their
+// launchers.
 #include "mnl_device.hpp"
 
 namespace mnl {
@@ -27,7 +28,7 @@ __global__ void dft_sample_kernel(const int *__restrict__ pj, const double *__re
   if (pj[3 * p] < 0) return;  // another rank's point
   const DftChunkDev cd = ch[pch[p]];
   const int c = cd.c, d = c % 3;
-  const bool mag = c >= 3;
+  const bool mag = c / 3 == T_H || c / 3 == T_B, raw = c / 3 >= T_D;  // raw: D or B itself
   Pt P;
   P.idx = 0;
   for (int e = 0; e < 3; e++) {
@@ -35,6 +36,7 @@ __global__ void dft_sample_kernel(const int *__restrict__ pj, const double *__re
     P.idx += (long long)P.j[e] * g.sdir[e];
   }
   auto val = [&](const Pt &q) -> double {
+    if (raw) return mag ? f.B[d][q.idx] : f.D[d][q.idx];
     if (mag) {
       const bool sep = f.H[d] && (f.hall || pml_at(f, g, d, qcoord(g, q, T_H, d, d)));
       return sep ? f.H[d][q.idx] : f.B[d][q.idx];
@@ -69,7 +71,9 @@ __global__ void dft_sample_kernel(const int *__restrict__ pj, const double *__re
 // -- the per-point table lookups of dft_sample_kernel (PML flags, ownership, fused box) done
 // once, so that the per-step sample is one metadata load and independent value loads.
 // sel: bits 0-1 component direction, 2-3 avgmode, 4 + 2v: kind of value v, 12-13 d1, 14-15
-// d2; 0xFFFF: another rank's point.  The chi1inv of implicit-E values: as the palette bytes of
+// d2; 0xFFFF: another rank's point.  A D component is kind 1 with chi1inv == 1.0 (x * 1.0 == x;
+// its palette byte is `one`'s, the entry that is bitwise 1.0), a B component kind 2 always, so
+// the sampler needs no further kind.  The chi1inv of implicit-E values: as the palette bytes of
 // the four values (spal, with uidx / utab: 4 B per point instead of 32) and as doubles (su,
 // the fallback); *bad is set when a palette value is not bitwise the chi1inv array's.
 __global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restrict__ pch,
@@ -78,7 +82,7 @@ __global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restric
                                 const double *__restrict__ utab, int *__restrict__ sidx,
                                 unsigned short *__restrict__ ssel, unsigned *__restrict__ spal,
                                 double4 *__restrict__ su, int *__restrict__ bad, Box cb,
-                                int *__restrict__ sci) {
+                                int *__restrict__ sci, unsigned one) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npts) return;
   if (pj[3 * p] < 0) {
@@ -91,7 +95,7 @@ __global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restric
   }
   const DftChunkDev cd = ch[pch[p]];
   const int c = cd.c, d = c % 3;
-  const bool mag = c >= 3;
+  const bool mag = c / 3 == T_H || c / 3 == T_B, raw = c / 3 >= T_D;
   Pt P;
   P.idx = 0;
   for (int e = 0; e < 3; e++) {
@@ -99,6 +103,7 @@ __global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restric
     P.idx += (long long)P.j[e] * g.sdir[e];
   }
   auto kind = [&](const Pt &q) -> unsigned {
+    if (raw) return mag ? 2u : 1u;
     if (mag) return (f.H[d] && (f.hall || pml_at(f, g, d, qcoord(g, q, T_H, d, d)))) ? 3u : 2u;
     return e_implicit(f, g, d, q) ? 1u : 0u;
   };
@@ -125,7 +130,9 @@ __global__ void dft_plan_kernel(const int *__restrict__ pj, const int *__restric
   for (int v = 0; v < nv; v++) {
     const unsigned k = kind(q[v]);
     sel |= k << (4 + 2 * v);
-    if (k == 1 && f.inveps[d]) {
+    if (k == 1 && raw) {
+      if (uidx) pal |= ((one >> (8 * d)) & 255u) << (8 * v);
+    } else if (k == 1 && f.inveps[d]) {
       uv[v] = f.inveps[d][q[v].idx];
       if (uidx) {
         const unsigned b = (uidx[q[v].idx] >> (8 * d)) & 255u;
@@ -249,10 +256,11 @@ __global__ void __launch_bounds__(256) dft_sample_jobs_kernel(DftSampleJobs J, D
 int k_dft_plan(const int *pj, const int *pch, const DftChunkDev *ch, long long npts,
                const DevGrid &g, const DevFields &f, const unsigned *uidx, const double *utab,
                int *sidx, unsigned short *ssel, unsigned *spal, void *su, int *bad,
-               const Box &cbox, int *sci, void *stream) {
+               const Box &cbox, int *sci, unsigned pal_one, void *stream) {
   if (npts <= 0) return 0;
   dft_plan_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      pj, pch, ch, npts, g, f, uidx, utab, sidx, ssel, spal, (double4 *)su, bad, cbox, sci);
+      pj, pch, ch, npts, g, f, uidx, utab, sidx, ssel, spal, (double4 *)su, bad, cbox, sci,
+      pal_one);
   return rc();
 }
 
@@ -642,6 +650,81 @@ __global__ void __launch_bounds__(256)
   double v = 0.0;
   for (int g = 0; g < nwg; g++) v += part[g * n + i];
   out[i] = v;
+}
+
+// ------------------------------------------------- pair sums (energy, force)
+// dft_energy::electric / magnetic (src/dft.cpp:657-687) and stress_sum (src/stress.cpp:90-99):
+// per frequency the sum over paired chunks and their points of x * real(a * conj(b)), read from
+// the DFT array where it lives.  The two chunks of a pair hold the same points in the same slot
+// order, so the host hands over runs (two slot bases, a count, x).  Lanes take consecutive pair
+// points -- consecutive slots of both chunks, so a wave's read of one frequency is one or two
+// contiguous 1-KB spans of 16-byte values per chunk -- and keep PS_FT frequencies in registers
+// over the workgroup's fixed range of pair points; then one wave reduction in registers and
+// one LDS pass over the PS_WAVES waves.  No atomics: part[wg][freq] is added in workgroup order
+// by n2f_reduce_kernel, and the split into workgroups depends on the object alone, so a value
+// is the same bits in every call and every stepping mode.
+template <int FT>
+__global__ void __launch_bounds__(64 * PS_WAVES)
+    dft_pair_sum_kernel(const double2 *__restrict__ dft, const PairRun *__restrict__ runs,
+                        int nruns, long long total, int wg_pts, int nfreq,
+                        double *__restrict__ part) {
+  __shared__ double red[PS_WAVES][FT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f0 = blockIdx.y * FT;
+  const long long g0 = (long long)blockIdx.x * wg_pts, g1 = min(g0 + (long long)wg_pts, total);
+  double acc[FT];
+#pragma unroll
+  for (int w = 0; w < FT; w++) acc[w] = 0.0;
+  for (long long g = g0 + threadIdx.x; g < g1; g += 64 * PS_WAVES) {
+    // the run of this pair point, by bisection every time: walking on from the previous
+    // point's run instead measured 2 to 2.6 times slower
+    int lo = 0, hi = nruns - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (runs[mid].g0 <= g)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    const PairRun r = runs[lo];
+    const long long sa = r.a0 + (g - r.g0), sb = r.b0 + (g - r.g0);
+    const double2 *__restrict__ pa = dft + (sa >> 6) * nfreq * 64 + (sa & 63);
+    const double2 *__restrict__ pb = dft + (sb >> 6) * nfreq * 64 + (sb & 63);
+    double2 a[FT], b[FT];
+#pragma unroll
+    for (int w = 0; w < FT; w++) {  // tail tiles repeat the last frequency (not written)
+      const long long fo = (long long)min(f0 + w, nfreq - 1) * 64;
+      a[w] = pa[fo];
+      b[w] = pb[fo];
+    }
+#pragma unroll
+    for (int w = 0; w < FT; w++) acc[w] += r.x * (a[w].x * b[w].x + a[w].y * b[w].y);
+  }
+#pragma unroll
+  for (int w = 0; w < FT; w++) {
+    const double v = n2f_wave_sum(acc[w]);
+    if (lane == 0) red[wave][w] = v;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < FT && f0 + t < nfreq) {
+    double v = red[0][t];
+#pragma unroll
+    for (int k = 1; k < PS_WAVES; k++) v += red[k][t];
+    part[(long long)blockIdx.x * nfreq + f0 + t] = v;
+  }
+}
+
+int k_dft_pair_sum(const double *dft, const PairRun *runs, int nruns, long long total, int wg_pts,
+                   int nwg, int nfreq, long long npad, double *part, void *stream) {
+  if (total <= 0 || nwg <= 0) return 0;
+  if (nfreq < 1 || nruns < 1 || wg_pts < 1 || npad < 64) return 2;
+  if ((long long)nwg * wg_pts < total) return 2;  // every pair point belongs to a workgroup
+  const dim3 grd((unsigned)nwg, (unsigned)((nfreq + PS_FT - 1) / PS_FT));
+  if (grd.y > 65535) return 2;
+  dft_pair_sum_kernel<PS_FT><<<grd, dim3(64 * PS_WAVES), 0, (hipStream_t)stream>>>(
+      (const double2 *)dft, runs, nruns, total, wg_pts, nfreq, part);
+  return rc();
 }
 
 int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream) {

@@ -13,7 +13,8 @@ namespace mnlh {
 //   need the high ghost plane (local nloc) <- rank+1's first plane (local 0).
 // kind 2 (before NR E update): D comps (and Lorentz P), both directions.
 // kind 3 (before a DFT update): H comps unshifted along the slab axis need the
-//   low ghost plane, which the centred-grid average reads (src/dft.cpp:281-287).
+//   low ghost plane, which the centred-grid average reads (src/dft.cpp:281-287);
+//   so do the D comps unshifted along it once a monitor samples D itself.
 int exchange(mnl_fields *F, int kind, hipStream_t st) {
   if (!st) st = F->stream;
   const DevGrid &g = F->g;
@@ -45,6 +46,8 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
         items.push_back({F->f.B[c], true});
         if (F->f.H[c]) items.push_back({F->f.H[c], true});
       }
+      if (F->dft_samples_d && c != sd && F->f.D[c] && F->allocated[3 * T_D + c])
+        items.push_back({F->f.D[c], true});
     } else {
       if (F->f.Dn[c] && F->allocated[3 * T_D + c]) items.push_back({F->f.Dn[c], c != sd});
       for (int k = 0; k < F->f.npol; k++)

@@ -330,6 +330,7 @@ AUTOMATIC = -1
 # python/simulation.py:65-67: opaque containers of get_flux_data / get_near2far_data
 FluxData = namedtuple("FluxData", ["E", "H"])
 NearToFarData = namedtuple("NearToFarData", ["F"])
+ForceData = namedtuple("ForceData", ["offdiag1", "offdiag2", "diag"])
 
 
 class _DftData:
@@ -461,6 +462,82 @@ class DftFields(_DftData):
                                                      self.yee_grid, self.decimation_factor)
 
 
+class ForceRegion(FluxRegion):
+    """python/simulation.py:571-594: a surface and the direction of the force to compute,
+    which must be given (it has no relation to the surface's orientation)."""
+
+
+class EnergyRegion(FluxRegion):
+    """python/simulation.py:597-611: a region to integrate the energy density over."""
+
+
+def _region_tuples(sim, regions, what, direction):
+    """(lo, hi, direction, weight) per region for the fields' add_dft_* calls"""
+    regs = []
+    for r in regions:
+        if r.weight.imag != 0:
+            raise NotImplementedError(f"complex {what} weights are out of scope (real fields)")
+        lo = [r.center[k] - 0.5 * r.size[k] for k in range(3)]
+        hi = [r.center[k] + 0.5 * r.size[k] for k in range(3)]
+        if sim.dimensions == 1:  # 1-D cells live on the z axis
+            lo, hi = [0.0, 0.0, lo[2]], [0.0, 0.0, hi[2]]
+        elif sim.dimensions == 2:
+            lo[2] = hi[2] = 0.0
+        regs.append((lo, hi, direction(r), r.weight.real))
+    return regs
+
+
+class DftForce(_DftData):
+    """python/simulation.py:726-760 (force object; fields::add_dft_force, src/stress.cpp:
+    153-191); the DFT lives on the GPU and force() sums there."""
+
+    nlists = 3
+
+    def __init__(self, sim, freq, regions, decimation_factor):
+        self.sim = sim
+        self.freq = [float(f) for f in freq]
+        self.regions = list(regions)
+        self.decimation_factor = decimation_factor
+        self.handle = None
+
+    def _create(self):
+        for r in self.regions:
+            if r.direction not in (X, Y, Z):
+                raise RuntimeError("meep: NO_DIRECTION dft_force is invalid")
+        regs = _region_tuples(self.sim, self.regions, "force", lambda r: r.direction)
+        self.handle = self.sim.fields.add_dft_force(regs, self.freq, self.decimation_factor)
+
+    def force(self):
+        return list(self._fields().dft_force(self.handle))
+
+
+class DftEnergy(_DftData):
+    """python/simulation.py:761-830 (energy object; fields::add_dft_energy, src/dft.cpp:
+    701-727); the DFT lives on the GPU and the three sums run there."""
+
+    nlists = 4
+
+    def __init__(self, sim, freq, regions, decimation_factor):
+        self.sim = sim
+        self.freq = [float(f) for f in freq]
+        self.regions = list(regions)
+        self.decimation_factor = decimation_factor
+        self.handle = None
+
+    def _create(self):
+        regs = _region_tuples(self.sim, self.regions, "energy", lambda r: 0)
+        self.handle = self.sim.fields.add_dft_energy(regs, self.freq, self.decimation_factor)
+
+    def electric(self):
+        return list(self._fields().dft_energy(self.handle, 0))
+
+    def magnetic(self):
+        return list(self._fields().dft_energy(self.handle, 1))
+
+    def total(self):
+        return list(self._fields().dft_energy(self.handle, 2))
+
+
 class Near2FarRegion(FluxRegion):
     """python/simulation.py:640-684: a near-field surface and its normal direction
     (AUTOMATIC: the one zero-size direction, volume::normal_direction)."""
@@ -571,6 +648,46 @@ def scale_flux_fields(s, flux):
     """python/simulation.py:5997-6003: the Fourier-transformed fields of flux times the
     complex s (load_minus_flux = load_flux, then s = -1)."""
     flux.scale_dfts(s)
+
+
+def scale_force_fields(s, force):
+    """python/simulation.py:6030-6039"""
+    force.scale_dfts(s)
+
+
+def get_force_freqs(f):
+    """python/simulation.py:6042-6047"""
+    return list(f.freq)
+
+
+def get_forces(f):
+    """python/simulation.py:6050-6056"""
+    return f.force()
+
+
+def scale_energy_fields(s, ef):
+    """python/simulation.py:6075-6076"""
+    ef.scale_dfts(s)
+
+
+def get_energy_freqs(f):
+    """python/simulation.py:6079-6084"""
+    return list(f.freq)
+
+
+def get_electric_energy(f):
+    """python/simulation.py:6087-6092"""
+    return f.electric()
+
+
+def get_magnetic_energy(f):
+    """python/simulation.py:6095-6100"""
+    return f.magnetic()
+
+
+def get_total_energy(f):
+    """python/simulation.py:6103-6110"""
+    return f.total()
 
 
 def scale_near2far_fields(s, near2far):
@@ -1306,6 +1423,89 @@ class Simulation:
         flux.load_hdf5(fname + ".mnl", -1)
 
     load_minus_mode = load_minus_flux
+
+    # -- force spectra (python/simulation.py:3357-3470)
+    def add_force(self, *args, **kwargs):
+        """add_force(fcen, df, nfreq, *ForceRegions, decimation_factor=0) or add_force(freq,
+        *ForceRegions, ...) -> fields::add_dft_force (src/stress.cpp:153-191); initialises the
+        fields first."""
+        args = fix_dft_args(args, 0)
+        freq, regions = args[0], args[1:]
+        force = DftForce(self, freq, regions, kwargs.get("decimation_factor", 0))
+        self.init_sim()
+        force._create()
+        self.dft_objects.append(force)
+        return force
+
+    def display_forces(self, *forces):
+        """The force spectra as "force<run_index>:" lines (frequency, then one column per
+        force object)."""
+        display_csv(self, "force", zip(get_force_freqs(forces[0]),
+                                       *[get_forces(f) for f in forces]))
+
+    def get_force_data(self, force):
+        """The Fourier-transformed fields of force as a ForceData of numpy arrays."""
+        return ForceData(offdiag1=force._get(0), offdiag2=force._get(1), diag=force._get(2))
+
+    def load_force_data(self, force, fdata):
+        self.init_sim()
+        for which, d in enumerate(fdata):
+            force._load(which, d)
+
+    def load_minus_force_data(self, force, fdata):
+        self.init_sim()
+        for which, d in enumerate(fdata):
+            force._load(which, d, -1)
+
+    def save_force(self, fname, force):
+        self.init_sim()
+        force.save_hdf5(fname + ".mnl")
+
+    def load_force(self, fname, force):
+        self.init_sim()
+        force.load_hdf5(fname + ".mnl")
+
+    def load_minus_force(self, fname, force):
+        self.init_sim()
+        force.load_hdf5(fname + ".mnl", -1)
+
+    # -- energy spectra (python/simulation.py:3109-3215)
+    def add_energy(self, *args, **kwargs):
+        """add_energy(fcen, df, nfreq, *EnergyRegions, decimation_factor=0) or add_energy(freq,
+        *EnergyRegions, ...) -> fields::add_dft_energy (src/dft.cpp:701-727); initialises the
+        fields first."""
+        args = fix_dft_args(args, 0)
+        freq, regions = args[0], args[1:]
+        energy = DftEnergy(self, freq, regions, kwargs.get("decimation_factor", 0))
+        self.init_sim()
+        energy._create()
+        self.dft_objects.append(energy)
+        return energy
+
+    def _display_energy(self, name, func, energys):
+        display_csv(self, f"{name}_energy", zip(get_energy_freqs(energys[0]),
+                                                *[func(e) for e in energys]))
+
+    def display_electric_energy(self, *energys):
+        self._display_energy("electric", get_electric_energy, energys)
+
+    def display_magnetic_energy(self, *energys):
+        self._display_energy("magnetic", get_magnetic_energy, energys)
+
+    def display_total_energy(self, *energys):
+        self._display_energy("total", get_total_energy, energys)
+
+    def save_energy(self, fname, energy):
+        self.init_sim()
+        energy.save_hdf5(fname + ".mnl")
+
+    def load_energy(self, fname, energy):
+        self.init_sim()
+        energy.load_hdf5(fname + ".mnl")
+
+    def load_minus_energy(self, fname, energy):
+        self.init_sim()
+        energy.load_hdf5(fname + ".mnl", -1)
 
     # -- and of a near2far object (python/simulation.py:3297-3355)
     def get_near2far_data(self, near2far):
