@@ -338,6 +338,23 @@ int mnl_fields_nr_fallbacks(mnl_fields *f, long long *count);
 /* Algorithmic bytes per owned cell per step of this configuration
  * (DESIGN.md "Roofline") and owned cells of this rank. */
 int mnl_fields_traffic_model(mnl_fields *f, double *bytes_per_cell_step, double *owned_cells);
+/* fields::use_bloch(d, k) (src/fields.cpp:75-90) for k = 0: both boundaries of direction dir
+ * (0 X, 1 Y, 2 Z) become Periodic.  No metal on those faces; each not-owned point is connected
+ * to the owned point one lattice vector away with phase 1 (connect_the_chunks,
+ * src/boundaries.cpp:347-623), and the ghost planes are copied on the device after the E and
+ * the H updates.  The fields stay real.  Accepted only before sources,
+ * DFT monitors and the first step.  Fails with a "meep: ..." message for k != 0 (complex fields
+ * are not supported), a PML on either side of the direction, a 1-D cell, a direction the cell
+ * does not have, the slab direction of fields on more than one rank, and (PML along two
+ * directions only) anisotropic susceptibilities or Newton-Raphson / off-diagonal chi1inv with a
+ * susceptibility.  One rank steps periodic
+ * 3-D runs in the fused mode like any other run (the top plane of each periodic direction as
+ * shell boxes); pairs of steps, and the fused mode on several ranks, are declined. */
+int mnl_fields_use_bloch(mnl_fields *f, int dir, double k_re, double k_im);
+/* boundary_condition of one side (0 low, 1 high) of a direction (src/meep.hpp: Periodic = 0,
+ * Metallic = 1); fails for a direction the cell does not have. */
+enum { MNL_BOUNDARY_PERIODIC = 0, MNL_BOUNDARY_METALLIC = 1 };
+int mnl_fields_boundary(mnl_fields *f, int dir, int side, int *kind);
 /* Allow (1, default) or forbid (0) the fused single-pass interior kernel
  * (used automatically for 3-D non-dispersive, non-NR configurations without
  * magnetic or integrated sources).  Results are identical either way. */

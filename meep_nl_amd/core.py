@@ -287,6 +287,20 @@ class Fields:
             lib().mnl_fields_destroy(self.h)
             self.h = None
 
+    # -- boundaries
+    def use_bloch(self, d, k=0):
+        """fields::use_bloch(d, k) (src/fields.cpp:75-90) for k = 0: both boundaries of
+        direction d (0 X, 1 Y, 2 Z) become periodic; the fields stay real.  Before sources,
+        DFT monitors and the first step."""
+        k = complex(k)
+        check(lib().mnl_fields_use_bloch(self.h, int(d), k.real, k.imag))
+
+    def boundary(self, d, side=0):
+        """'periodic' or 'metallic': the boundary condition of one side of direction d."""
+        v = ctypes.c_int(0)
+        check(lib().mnl_fields_boundary(self.h, int(d), int(side), ctypes.byref(v)))
+        return "periodic" if v.value == 0 else "metallic"
+
     # -- sources
     def add_point_source(self, comp, kind, params, pos, amp=1.0, is_integrated=False):
         p = np.ascontiguousarray(params, dtype=np.float64)

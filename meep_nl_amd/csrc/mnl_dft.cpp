@@ -93,6 +93,8 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
   else
     yd[0] = 0, yd[1] = 1, yd[2] = 2;
   std::vector<DftChunkH> made;
+  LatticeShifts ls(S, F->periodic, wmin, wmax);  // src/loop_in_chunks.cpp:390-532
+  do {
   for (auto &ch : reference_chunks(S)) {
     int isc[3], iec[3];
     double s0c[3], s1c[3], e0c[3], e1c[3];
@@ -107,23 +109,24 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
       const int uoc = S.io[d] + 2 - sh[d], coc = ch[d] + 2 - sh[d],
                 cbo = ch[d] + 2 * ch[3 + d] - sh[d];
       const int iscoS = std::max(uoc, std::min(coc, cbo)), iecoS = std::max(coc, cbo);
-      isc[d] = std::max(is[d], iscoS);
-      iec[d] = std::min(ie[d], iecoS);
+      isc[d] = std::max(is[d] - ls.shifti[d], iscoS);
+      iec[d] = std::min(ie[d] - ls.shifti[d], iecoS);
       if (isc[d] > iec[d]) emp = true;
     }
     if (emp) continue;
     for (int d = 0; d < 3; d++) {
       if (!S.has[d]) continue;
-      if (isc[d] == is[d]) {
+      const int iscS = isc[d] + ls.shifti[d], iecS = iec[d] + ls.shifti[d];
+      if (iscS == is[d]) {
         s0c[d] = s0[d];
         s1c[d] = s1[d];
-      } else if (isc[d] == is[d] + 2) {
+      } else if (iscS == is[d] + 2) {
         s0c[d] = s1[d];
       }
-      if (iec[d] == ie[d]) {
+      if (iecS == ie[d]) {
         e0c[d] = e0[d];
         e1c[d] = e1[d];
-      } else if (iec[d] == ie[d] - 2) {
+      } else if (iecS == ie[d] - 2) {
         e0c[d] = e1[d];
       }
       if (iec[d] == isc[d]) {
@@ -148,6 +151,7 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
     dc.avgmode = nun;
     for (int d = 0; d < 3; d++) {
       dc.is[d] = isc[d], dc.ie[d] = iec[d];
+      dc.shifti[d] = ls.shifti[d];
       dc.s0[d] = s0c[d], dc.s1[d] = s1c[d], dc.e0[d] = e0c[d], dc.e1[d] = e1c[d];
     }
     dc.dV0 = dV0;
@@ -201,13 +205,14 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
           }
           for (int d = 0; d < 3; d++) pj.push_back(mine ? j[d] : -1);
           if (o.n2f)
-            for (int d = 0; d < 3; d++) o.h_pp.push_back(p[d]);
+            for (int d = 0; d < 3; d++) o.h_pp.push_back(p[d] + ls.shifti[d]);
         }
     dc.p0 = o.h_pj.size() / 3;
     o.h_pj.insert(o.h_pj.end(), pj.begin(), pj.end());
     pw.insert(pw.end(), w.begin(), w.end());
     made.push_back(dc);
   }
+  } while (ls.next());
   for (auto &m : made) list.insert(list.begin(), m);
 }
 
@@ -613,7 +618,8 @@ int dft_points(mnl_fields *F, int h, int which, double *out, long long npoints) 
           for (int q = 0; q < 3; q++) {
             const int d = yd[q];
             wl[q] = loop_w1(dc.s0[d], dc.s1[d], dc.e0[d], dc.e1[d], ii[q], n[q]);
-            out[5 * k + d] = S.has[d] ? (dc.is[d] + 2 * ii[q]) * (0.5 * (1.0 / S.a)) : 0.0;
+            out[5 * k + d] =
+                S.has[d] ? (dc.is[d] + dc.shifti[d] + 2 * ii[q]) * (0.5 * (1.0 / S.a)) : 0.0;
           }
           double w = dc.incl ? wl[2] * (wl[1] * ((dc.dV0 + 0.0 * i2) * wl[0])) : 1.0;
           if (dc.sqrt_w) w = sqrt(w);
@@ -1079,6 +1085,10 @@ int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long di
     if (dc.c == c) L.push_back(&dc);
   for (auto &dc : o.H)
     if (dc.c == c) L.push_back(&dc);
+  for (auto *dc : L)
+    if (dc->shifti[0] || dc->shifti[1] || dc->shifti[2])
+      return fail("get_dft_array: a region that reaches a periodic face (image chunks) is not "
+                  "supported");
   int mn[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, mx[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
   for (auto *dc : L)
     for (int d = 0; d < 3; d++) mn[d] = std::min(mn[d], dc->is[d]), mx[d] = std::max(mx[d], dc->ie[d]);

@@ -294,6 +294,25 @@ static bool make_fused_boxes(mnl_fields *F) {
     bl.start[1] = (long long)g.N[0] * g.N[1];
     bl.n = 1;
   }
+  // ... and the top plane of every periodic axis (one rank): plane n of the unshifted
+  // components is owned there, and its D needs the wrapped B / H of plane 0 first.  The boxes
+  // are disjoint: a later one leaves out the planes of the earlier ones.
+  if (F->nranks == 1 && any_periodic(F)) {
+    Box cur;
+    for (int k = 0; k < 3; k++) cur.lo[k] = 0, cur.hi[k] = g.N[k] - 1;
+    long long acc = 0;
+    for (int k = 2; k >= 0; k--) {  // 3-D: device axis k is direction k
+      if (!F->periodic[k]) continue;
+      Box b = cur;
+      b.lo[k] = b.hi[k] = g.N[k] - 1;
+      bl.b[bl.n] = b;
+      bl.start[bl.n] = acc;
+      acc += (long long)(b.hi[0] - b.lo[0] + 1) * (b.hi[1] - b.lo[1] + 1) * (b.hi[2] - b.lo[2] + 1);
+      bl.n++;
+      cur.hi[k] = g.N[k] - 2;
+    }
+    bl.start[bl.n] = acc;
+  }
   return true;
 }
 
@@ -355,6 +374,9 @@ static bool nr_fused_ok(mnl_fields *F) {
 
 static bool fused_possible(mnl_fields *F) {
   if (!F->allow_fused || F->S.dim != 3 || F->upnl || F->f.aniso || F->hall) return false;
+  // periodic directions: one rank; the chi(2) box's neighbour reads
+  // would need the D / P ghosts inside the fused step
+  if (any_periodic(F) && (F->nranks > 1 || F->nr)) return false;
   if (F->nr && !nr_fused_ok(F)) return false;
   for (int t = 0; t < 2; t++)
     for (int d = 0; d < 3; d++)

@@ -567,6 +567,7 @@ int mnl_fields_copy_component(mnl_fields *F, int comp, double *host, size_t n) {
     F->scratch_cap = nt;
   }
   HIPCHK(hipMemsetAsync(F->d_scratch, 0, nt * sizeof(double), F->stream));
+  if (wrap_for_readers(F)) return -1;  // periodic: the not-owned planes read as their owners
   const bool fe = F->fused && t == T_E;
   if (k_to_canonical(F->d_scratch, src, hsep, F->g, t, d, F->f, fe ? &F->fusedG : nullptr,
                      fe ? F->f.D[d] : nullptr, fe ? F->f.inveps[d] : nullptr, F->stream))
@@ -615,6 +616,49 @@ int mnl_fields_nr_fallbacks(mnl_fields *F, long long *count) {
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   HIPCHK(hipMemcpy(&v, F->d_nr_fallbacks, sizeof(v), hipMemcpyDeviceToHost));
   *count = (long long)v;
+  return 0;
+}
+
+int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
+  // fields::use_bloch (src/fields.cpp:75-90) with k = 0
+  if (!F) return fail("null fields");
+  if (dir < 0 || dir > 2) return fail("use_bloch: direction must be 0 (X), 1 (Y) or 2 (Z)");
+  if (k_re != 0.0 || k_im != 0.0)
+    return fail("use_bloch: k != 0 needs complex fields, which are not supported (only k = 0, "
+                "real fields)");
+  if (F->S.dim == 1) return fail("use_bloch: periodic boundaries of 1-D cells are not supported");
+  if (!F->S.has[dir]) return fail("use_bloch: the cell has no such direction");
+  if (F->S.pml_thick[dir][0] > 0 || F->S.pml_thick[dir][1] > 0)
+    return fail("use_bloch: a PML along a periodic direction is not supported");
+  if (F->nranks > 1 && dir == F->slab_dir)
+    return fail("use_bloch: the slab direction of fields on more than one rank cannot be "
+                "periodic");
+  if (F->periodic[dir]) return 0;
+  {
+    // The E / P kernels that read wall-plane neighbours of another reference chunk as 0
+    // (on_wall: anisotropic sigma, and Newton-Raphson or upstream off-diagonal chi1inv with a
+    // susceptibility) take plane n of a direction for a wall.  Such a neighbour exists only
+    // where two other directions are split into PML chunks.
+    int npml = 0;
+    for (int d = 0; d < 3; d++) npml += F->S.has[d] && F->pml_any[d];
+    if (npml >= 2 && (F->f.aniso || F->f.wall_e))
+      return fail("use_bloch: anisotropic susceptibilities, and Newton-Raphson or off-diagonal "
+                  "chi1inv with a susceptibility, are not supported in a periodic cell with PML "
+                  "along two directions");
+  }
+  if (F->t != 0 || F->e_first_done || F->h_first_done || F->u_first_done[0] || F->u_first_done[1])
+    return fail("use_bloch: only before the first step");
+  if (!F->groups.empty() || !F->dfts.empty())
+    return fail("use_bloch: only before sources and DFT monitors are added");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (F->fused && set_fused(F, false)) return -1;
+  return set_periodic(F, dir);
+}
+
+int mnl_fields_boundary(mnl_fields *F, int dir, int side, int *kind) {
+  if (!F || !kind || dir < 0 || dir > 2 || side < 0 || side > 1) return fail("bad argument");
+  if (!F->S.has[dir]) return fail("boundary: the cell has no such direction");
+  *kind = F->periodic[dir] ? MNL_BOUNDARY_PERIODIC : MNL_BOUNDARY_METALLIC;
   return 0;
 }
 

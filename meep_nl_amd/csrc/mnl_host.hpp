@@ -207,6 +207,8 @@ struct DftChunkH {
   int c0 = -1;       // near2far: the equivalent current's component (dft_chunk::vc)
   bool sqrt_w = false;  // sqrt_dV_and_interp_weights: the loop weight's square root is applied
   double extra = 1.0;   // dft_chunk::extra_weight (used by the force sum only)
+  int shifti[3] = {0, 0, 0};  // periodic image chunk: the lattice shift from a loop point to
+                              // the point of the region it stands for (dft_chunk::shift)
 };
 enum { DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4 };
 constexpr int DFT_MAXLISTS = 4;
@@ -303,6 +305,10 @@ struct mnl_fields {
   int rank = 0, nranks = 1;
   std::unique_ptr<Comm> comm;
   int slab_dir = 2;  // direction decomposed across ranks
+  // fields::use_bloch with k = 0: both boundaries of the direction are
+  // Periodic -- no metal wall, plane n of the unshifted components owned, the not-owned planes
+  // copies of the owner one lattice vector away (wrap)
+  bool periodic[3] = {false, false, false};
   DevGrid g;
   DevFields f;
   size_t nlocal = 0;  // doubles per local array
@@ -687,6 +693,9 @@ int dev_alloc(mnl_fields *F, T **p, size_t n, bool zero = true) {
   return 0;
 }
 
+inline bool any_periodic(const mnl_fields *F) {
+  return F->periodic[0] || F->periodic[1] || F->periodic[2];
+}
 inline int check_comp(int c) {
   if (c < 0 || c >= MNL_NUM_COMPONENTS) return fail("invalid component");
   return 0;
@@ -706,6 +715,7 @@ void slab_range(int ncell, int rank, int nranks, int *lo, int *hi);
 bool has_field(const mnl_structure &S, int c);
 int require_component(mnl_fields *F, int c);
 int finalize_fields(mnl_fields *F);
+int set_periodic(mnl_fields *F, int dir);
 int initialize_field(mnl_fields *F, int c, const double *host);
 MNL_HIDDEN int sphere_quadrature(int dim, double *xyzw);
 MNL_HIDDEN int set_epsilon_geometry(mnl_structure *s, int device, int nobj, const double *objs,
@@ -743,6 +753,9 @@ int tb_chain_join(mnl_fields *F);
 // ---- mnl_step.cpp: the step path and the NaN guard
 constexpr int NR_HARD_CAP = 4096;  // deferred NR problems per E update (more: solved in place)
 int exchange(mnl_fields *F, int kind, hipStream_t st = nullptr);
+constexpr int WRAP_ALL = 5;  // wrap kind: every field and polarization array (readers, checkpoints)
+int wrap(mnl_fields *F, int kind, hipStream_t st = nullptr);
+int wrap_for_readers(mnl_fields *F);
 int h_lazy_copy(mnl_fields *F);
 int u_lazy_copy(mnl_fields *F, int which);
 int e_lazy_copy(mnl_fields *F);
@@ -770,6 +783,39 @@ MNL_HIDDEN void tb_info(const mnl_fields *F, double v[MNL_NUM_TBINFO]);
 MNL_HIDDEN int fields_mode(const mnl_fields *F);
 
 // ---- mnl_dft.cpp: loop_in_chunks helpers and DFT monitors
+// loop_in_chunks' loop over lattice shifts (src/loop_in_chunks.cpp:390-412, 525-532): per
+// periodic direction the shifts for which the cell's image meets [wmin, wmax], the first
+// direction fastest; shifti in half-coordinates.  A shift whose image misses the region's
+// grid points gives empty chunk loops, which the callers skip as the reference does.
+struct LatticeShifts {
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, cur[3] = {0, 0, 0}, shifti[3] = {0, 0, 0};
+  int iL[3] = {0, 0, 0};
+  LatticeShifts(const mnl_structure &S, const bool per[3], const double wmin[3],
+                const double wmax[3]) {
+    for (int d = 0; d < 3; d++) {
+      if (!S.has[d] || !per[d]) continue;
+      const double L = S.n[d] * (1.0 / S.a);
+      const double gmin = S.io[d] * (0.5 * (1.0 / S.a)), gmax = gmin + L;
+      lo[d] = int(floor((wmin[d] - gmax) / L));
+      hi[d] = int(ceil((wmax[d] - gmin) / L));
+      iL[d] = 2 * S.n[d];
+      cur[d] = lo[d];
+      shifti[d] = iL[d] * cur[d];
+    }
+  }
+  bool next() {  // false after the last shift
+    for (int d = 0; d < 3; d++) {
+      if (cur[d] + 1 <= hi[d]) {
+        cur[d]++;
+        shifti[d] = iL[d] * cur[d];
+        return true;
+      }
+      cur[d] = lo[d];
+      shifti[d] = iL[d] * cur[d];
+    }
+    return false;
+  }
+};
 inline int my_round(double x) { return int(floor(fabs(x) + 0.5) * (x < 0 ? -1 : 1)); }
 inline size_t dft_at(size_t p, size_t i, size_t nf) { return ((p >> 6) * nf + i) * 64 + (p & 63); }
 void dft_boundary_weights(const mnl_structure &S, const double wmin[3], const double wmax[3],

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "mnl_pair_runs.hpp"
+#include "mnl_wrap.hpp"
 
 namespace mnl {
 
@@ -44,7 +45,9 @@ struct DevGrid {
   long long sdir[3];    // stride per direction X,Y,Z (0 if absent)
   int off[3];           // global index of local index 0, per direction
   int nglob[3];         // global cells per direction
-  int wall[3];          // 1: metallic wall plane (global index n) excluded from updates
+  int wall[3];          // 1: metallic wall plane (global index n) excluded from updates; 0 on a
+                        // present direction: periodic (plane n of the unshifted components is
+                        // owned, the not-owned planes are copies, wrap_kernel)
   int owned_lo_sh[3];   // per direction: local owned range of shifted components
   int owned_hi_sh[3];
   int owned_lo_un[3];   // ... of unshifted components (wall excluded)
@@ -618,5 +621,7 @@ int k_to_box(double *dst, const double *src, const double *hsep, const DevGrid &
 int k_average(double *f, const double *bk, long long n, void *stream);
 int k_copy(double *dst, const double *src, long long n, void *stream);
 int k_fill(double *p, double v, size_t n, void *stream);
+// the periodic ghost planes of the listed arrays (thread table: wrap_plan, mnl_wrap.hpp)
+int k_wrap(const WrapArgs &w, void *stream);
 
 }  // namespace mnl

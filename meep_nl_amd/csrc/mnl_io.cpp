@@ -80,8 +80,13 @@ int ckpt_quiesce(mnl_fields *F) {
   if (set_fused(F, false)) return -1;
   for (auto &op : F->dfts)
     if (dft_flush(F, *op)) return -1;
+  if (wrap(F, WRAP_ALL)) return -1;  // periodic: the not-owned planes as step_boundaries leaves them
   HIPCHK(hipStreamSynchronize(F->stream));
   return 0;
+}
+
+static int ckpt_periodic_mask(const mnl_fields *F) {
+  return (F->periodic[0] ? 1 : 0) | (F->periodic[1] ? 2 : 0) | (F->periodic[2] ? 4 : 0);
 }
 
 int fields_dump(mnl_fields *F, const char *path) {
@@ -90,8 +95,16 @@ int fields_dump(mnl_fields *F, const char *path) {
   FILE *fp = fopen(path, "wb");
   if (!fp) return fail(std::string("cannot create fields output file ") + path);
   std::unique_ptr<FILE, int (*)(FILE *)> guard(fp, fclose);
-  CkHeader h = ckpt_header(F, (int)es.size());
+  // a run with periodic directions records them in a leading entry without data (kind 14,
+  // a = bit per direction); a run without writes the bytes it always wrote
+  const int pmask = ckpt_periodic_mask(F);
+  CkHeader h = ckpt_header(F, (int)es.size() + (pmask ? 1 : 0));
   if (fwrite(&h, sizeof h, 1, fp) != 1) return fail("write error");
+  if (pmask) {
+    const int32_t id[3] = {14, pmask, 0};
+    const uint64_t n = 0;
+    if (fwrite(id, sizeof id, 1, fp) != 1 || fwrite(&n, 8, 1, fp) != 1) return fail("write error");
+  }
   std::vector<double> buf;
   for (auto &e : es) {
     int32_t id[3] = {e.kind, e.a, e.b};
@@ -128,6 +141,11 @@ int fields_load(mnl_fields *F, const char *path) {
     int32_t id[3];
     uint64_t n;
     if (fread(id, sizeof id, 1, fp) != 1 || fread(&n, 8, 1, fp) != 1) return fail("read error");
+    // the boundary kinds come first, before anything is copied (no entry: none periodic)
+    if (k == 0 && (id[0] == 14 ? id[1] : 0) != ckpt_periodic_mask(F))
+      return fail("fields file was written with other boundary kinds (its periodic directions "
+                  "differ from these fields')");
+    if (id[0] == 14) continue;
     const CkEntry *dst = nullptr;
     for (auto &e : es)
       if (e.kind == id[0] && e.a == id[1] && e.b == id[2]) dst = &e;
@@ -146,6 +164,8 @@ int fields_load(mnl_fields *F, const char *path) {
   // already separate (a dump taken before the first step holds zeros in them)
   F->e_first_done = F->h_first_done = true;
   F->u_first_done[0] = F->u_first_done[1] = true;
+  if (wrap(F, WRAP_ALL)) return -1;
+  HIPCHK(hipStreamSynchronize(F->stream));
   return 0;
 }
 
@@ -443,6 +463,7 @@ int copy_component_box(mnl_fields *F, int c, const int lo[3], const int hi[3],
   HIPCHK(hipMalloc(&buf, (size_t)n * sizeof(double)));
   std::unique_ptr<void, void (*)(void *)> guard(buf, [](void *p) { (void)hipFree(p); });
   HIPCHK(hipMemsetAsync(buf, 0, (size_t)n * sizeof(double), F->stream));
+  if (wrap_for_readers(F)) return -1;  // periodic: the not-owned planes read as their owners
   const bool fe = F->fused && t == T_E;
   if (k_to_box(buf, src, hsep, F->g, t, d, F->f, fe ? &F->fusedG : nullptr, fe ? F->f.D[d] : nullptr,
                fe ? F->f.inveps[d] : nullptr, lo, hi, hs, F->stream))
@@ -1014,6 +1035,7 @@ int sync_magnetic(mnl_fields *F, MagBackup &bk) {
   // one B step at time(): step_db(B) + step_source(B) + step_boundaries(B) +
   // update_eh(H) + step_boundaries(H)
   if (F->nranks > 1 && exchange(F, 0)) return fail("E halo exchange failed");
+  if (wrap(F, 0)) return -1;
   if (!F->u_first_done[0] && u_lazy_copy(F, 0)) return -1;
   const DevGrid &g = F->g;
   if (k_curl(T_B, F->interior, nullptr, g, f, F->planB, F->S.courant, F->stream) ||
@@ -1039,6 +1061,7 @@ int sync_magnetic(mnl_fields *F, MagBackup &bk) {
   if (!F->h_first_done && h_lazy_copy(F)) return -1;
   if (update_h_any(F, F->shell_list, false)) return -1;  // no update_pols here (reference)
   if (F->nranks > 1 && exchange(F, 1)) return fail("H halo exchange failed");
+  if (wrap(F, 1)) return -1;
   for (auto &a : bk.avg)
     if (k_average(a.first, a.second, (long long)n, F->stream)) return fail("average launch failed");
   HIPCHK(hipStreamSynchronize(F->stream));

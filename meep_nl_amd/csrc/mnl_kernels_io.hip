@@ -1,6 +1,6 @@
 // mnl_kernels_io.hip -- gfx950 kernels behind mnl_io.cpp and the ABI's getters: the energy
 // integral, device layout -> a box of the whole-cell array (and the canonical layout), and the
-// elementwise average / copy / fill, with their launchers.
+// elementwise average / copy / fill, and the periodic ghost wrap, with their launchers.
 #include "mnl_device.hpp"
 
 namespace mnl {
@@ -32,6 +32,7 @@ __global__ void to_box_kernel(double *dst, const double *src, const double *hsep
     int lo = sh ? g.owned_lo_sh[d] : g.owned_lo_un[d];
     int hi = sh ? g.owned_hi_sh[d] : g.owned_hi_un[d];
     if (!sh && g.wall[d] && p.j[d] + g.off[d] == g.nglob[d]) hi = p.j[d];  // wall plane (= 0)
+    if (!g.wall[d]) lo = 0, hi = g.nglob[d];  // periodic: the not-owned plane is the owner's copy
     if (p.j[d] < lo || p.j[d] > hi) return;
   }
   const long long bs[3] = {bs0, bs1, bs2};
@@ -153,6 +154,36 @@ __global__ void copy_kernel(double *dst, const double *src, long long n) {
 int k_copy(double *dst, const double *src, long long n, void *stream) {
   if (n <= 0) return 0;
   copy_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(dst, src, n);
+  return rc();
+}
+
+// ------------------------------------------------------------- periodic ghost wrap
+// step_boundaries over the periodic connections (src/boundaries.cpp:347-623 with phase 1): one
+// launch, one thread per ghost point (x faces) or pair of ghost points (y / z faces) of every
+// listed array; the thread table is wrap_points (mnl_wrap.hpp).  Sources are owned points, so
+// no thread reads what another one writes.
+__global__ __launch_bounds__(256) void wrap_kernel(WrapArgs w, long long total) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  int arr;
+  long long dst[2], src[2];
+  const int np = wrap_points(w, t, arr, dst, src);
+  if (np == 0) return;
+  double *p = w.a[arr].p;
+  if (np == 2 && dst[1] == dst[0] + 1 && src[1] == src[0] + 1 &&
+      (((unsigned long long)(p + dst[0]) | (unsigned long long)(p + src[0])) & 15ull) == 0) {
+    *reinterpret_cast<double2 *>(p + dst[0]) = *reinterpret_cast<const double2 *>(p + src[0]);
+    return;
+  }
+  for (int k = 0; k < np; k++) p[dst[k]] = p[src[k]];
+}
+
+int k_wrap(const WrapArgs &w, void *stream) {
+  if (w.n <= 0 || w.n > WRAP_MAXA || w.fstart[3] <= 0) return w.n > WRAP_MAXA ? 2 : 0;
+  for (int a = 0; a < 3; a++)
+    if (w.per[a] && w.N[a] < 2) return 2;
+  const long long total = w.fstart[3] * w.n;
+  wrap_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, total);
   return rc();
 }
 

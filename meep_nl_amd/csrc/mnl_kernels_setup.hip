@@ -309,7 +309,7 @@ __global__ void init_add_kernel(double *dst, double *alt, const double *src, Dev
     p.j[d] = g.ax[d] >= 0 ? ii[g.ax[d]] : 0;
     if (g.ax[d] < 0) continue;
     cidx += (long long)(p.j[d] + g.off[d]) * cs[d];
-    if (!shift_of(type, c, d) && p.j[d] + g.off[d] == g.nglob[d]) wall = true;
+    if (!shift_of(type, c, d) && g.wall[d] && p.j[d] + g.off[d] == g.nglob[d]) wall = true;
   }
   double *t = dst;
   bool sep = pml_at(f, g, c, qcoord(g, p, type, c, c));

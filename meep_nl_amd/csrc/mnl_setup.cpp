@@ -127,7 +127,7 @@ static void setup_grid(mnl_fields *F) {
   for (int d = 0; d < 3; d++) {
     if (!S.has[d]) continue;
     g.nglob[d] = S.n[d];
-    g.wall[d] = 1;
+    g.wall[d] = F->periodic[d] ? 0 : 1;
     if (d == F->slab_dir) {
       g.off[d] = lo_cell;
       Nax[g.ax[d]] = hi_cell - lo_cell + 1;
@@ -135,14 +135,15 @@ static void setup_grid(mnl_fields *F) {
       g.owned_lo_sh[d] = 0;
       g.owned_hi_sh[d] = nloc - 1;
       g.owned_lo_un[d] = 1;
-      g.owned_hi_un[d] = (hi_cell == S.n[d]) ? nloc - 1 : nloc;  // global wall plane excluded
+      // global wall plane excluded (a periodic direction has none: plane n is owned)
+      g.owned_hi_un[d] = (hi_cell == S.n[d] && !F->periodic[d]) ? nloc - 1 : nloc;
     } else {
       g.off[d] = 0;
       Nax[g.ax[d]] = S.n[d] + 1;
       g.owned_lo_sh[d] = 0;
       g.owned_hi_sh[d] = S.n[d] - 1;
       g.owned_lo_un[d] = 1;
-      g.owned_hi_un[d] = S.n[d] - 1;
+      g.owned_hi_un[d] = F->periodic[d] ? S.n[d] : S.n[d] - 1;
     }
   }
   for (int k = 0; k < 3; k++) g.N[k] = Nax[k];
@@ -153,6 +154,15 @@ static void setup_grid(mnl_fields *F) {
   g.st[2] = p0 * g.N[1];
   F->nlocal = size_t(p0) * g.N[1] * g.N[2];
   for (int d = 0; d < 3; d++) g.sdir[d] = g.ax[d] >= 0 ? g.st[g.ax[d]] : 0;
+}
+
+// fields::use_bloch(d, 0) (src/fields.cpp:75-90): the ownership ranges of the grid change, the
+// array extents, the boxes (PML only) and everything allocated do not
+int set_periodic(mnl_fields *F, int dir) {
+  F->periodic[dir] = true;
+  setup_grid(F);
+  F->tb_sig = 0;
+  return 0;
 }
 
 static void make_shell_list(mnl_fields *F) {
@@ -816,6 +826,7 @@ int initialize_field(mnl_fields *F, int c, const double *host) {
     const int kind = t == T_E ? 0 : t == T_D ? 2 : 1;
     if (exchange(F, kind)) return fail("initialize_field halo exchange failed");
   }
+  if (wrap(F, t == T_E ? 0 : t == T_D ? 2 : 3)) return -1;
   ISrcDev is{};
   if (t == T_D) {  // update_eh(E_stuff); step_boundaries(E_stuff)
     if (!F->e_first_done && e_lazy_copy(F)) return -1;
@@ -826,10 +837,12 @@ int initialize_field(mnl_fields *F, int c, const double *host) {
     if (nr_defer_end(F)) return -1;
     if (f.wall_e && k_aniso_wall(F->g, f, 1, F->stream)) return fail("wall E launch failed");
     if (F->nranks > 1 && exchange(F, 0)) return fail("E halo exchange failed");
+    if (wrap(F, 0)) return -1;
   } else if (t == T_B) {  // update_eh(H_stuff); step_boundaries(H_stuff)
     if (!F->h_first_done && h_lazy_copy(F)) return -1;
     if (update_h_any(F, F->shell_list, false)) return -1;  // update_eh(H_stuff) only
     if (F->nranks > 1 && exchange(F, 1)) return fail("H halo exchange failed");
+    if (wrap(F, 1)) return -1;
   } else {
     F->force_unfused_next = true;  // E (or H) differs from what D (B) implies
   }

@@ -6,10 +6,13 @@ namespace mnlh {
 
 // ------------------------------------------------------------- loop_in_chunks
 // One reference chunk's loop of fields::loop_in_chunks over [wmin, wmax] on
-// component c's Yee grid (src/loop_in_chunks.cpp:325-520; no symmetry, no
-// Bloch): half-coordinate range [isc, iec] and the boundary weights.
+// component c's Yee grid (src/loop_in_chunks.cpp:325-520; no symmetry, Bloch
+// phase 1): half-coordinate range [isc, iec] and the boundary weights.  Along a
+// periodic direction the loop over lattice shifts (390-532) adds the chunks'
+// images: shifti is the shift (half-coordinates) from a loop point to the point
+// of `where` it stands for.
 struct CLoop {
-  int isc[3], iec[3];
+  int isc[3], iec[3], shifti[3];
   double s0[3], s1[3], e0[3], e1[3];
   double W(int d, long i) const {  // IVEC_LOOP_WEIGHT1x (src/meep/vec.hpp:372-378)
     const long n = (iec[d] - isc[d]) / 2 + 1;
@@ -18,8 +21,8 @@ struct CLoop {
   }
 };
 
-static std::vector<CLoop> chunk_loops(const mnl_structure &S, int c, const double wmin[3],
-                                      const double wmax[3]) {
+static std::vector<CLoop> chunk_loops(const mnl_structure &S, const bool per[3], int c,
+                                      const double wmin[3], const double wmax[3]) {
   int is[3] = {0, 0, 0}, ie[3] = {0, 0, 0};
   for (int d = 0; d < 3; d++) {
     if (!S.has[d]) continue;
@@ -31,11 +34,14 @@ static std::vector<CLoop> chunk_loops(const mnl_structure &S, int c, const doubl
   double s0[3], s1[3], e0[3], e1[3];
   dft_boundary_weights(S, wmin, wmax, is, ie, s0, e0, s1, e1);
   std::vector<CLoop> out;
+  LatticeShifts ls(S, per, wmin, wmax);
+  do {
   for (auto &ch : reference_chunks(S)) {
     CLoop L;
     bool emp = false;
     for (int d = 0; d < 3; d++) {
       L.s0[d] = L.s1[d] = L.e0[d] = L.e1[d] = 1.0;
+      L.shifti[d] = ls.shifti[d];
       if (!S.has[d]) {
         L.isc[d] = L.iec[d] = 0;
         continue;
@@ -45,23 +51,24 @@ static std::vector<CLoop> chunk_loops(const mnl_structure &S, int c, const doubl
       const int sh = S.shift(c, d);
       const int uoc = S.io[d] + 2 - sh, coc = ch[d] + 2 - sh, cbo = ch[d] + 2 * ch[3 + d] - sh;
       const int iscoS = std::max(uoc, std::min(coc, cbo)), iecoS = std::max(coc, cbo);
-      L.isc[d] = std::max(is[d], iscoS);
-      L.iec[d] = std::min(ie[d], iecoS);
+      L.isc[d] = std::max(is[d] - ls.shifti[d], iscoS);
+      L.iec[d] = std::min(ie[d] - ls.shifti[d], iecoS);
       if (L.isc[d] > L.iec[d]) emp = true;
     }
     if (emp) continue;
     for (int d = 0; d < 3; d++) {
       if (!S.has[d]) continue;
-      if (L.isc[d] == is[d]) {
+      const int iscS = L.isc[d] + ls.shifti[d], iecS = L.iec[d] + ls.shifti[d];
+      if (iscS == is[d]) {
         L.s0[d] = s0[d];
         L.s1[d] = s1[d];
-      } else if (L.isc[d] == is[d] + 2) {
+      } else if (iscS == is[d] + 2) {
         L.s0[d] = s1[d];
       }
-      if (L.iec[d] == ie[d]) {
+      if (iecS == ie[d]) {
         L.e0[d] = e0[d];
         L.e1[d] = e1[d];
-      } else if (L.iec[d] == ie[d] - 2) {
+      } else if (iecS == ie[d] - 2) {
         L.e0[d] = e1[d];
       }
       if (L.iec[d] == L.isc[d]) {
@@ -79,6 +86,7 @@ static std::vector<CLoop> chunk_loops(const mnl_structure &S, int c, const doubl
     }
     out.push_back(L);
   }
+  } while (ls.next());
   return out;
 }
 
@@ -121,7 +129,7 @@ static int add_volume_source(mnl_fields *F, int c, int st, const double wmin0[3]
   SrcGroup grp;
   grp.comp = c;
   grp.st = st;
-  for (const CLoop &L : chunk_loops(S, c, wmin, wmax)) {
+  for (const CLoop &L : chunk_loops(S, F->periodic, c, wmin, wmax)) {
     long ln[3];
     for (int k = 0; k < 3; k++) ln[k] = S.has[yd[k]] ? (L.iec[yd[k]] - L.isc[yd[k]]) / 2 + 1 : 1;
     for (long i1 = 0; i1 < ln[0]; i1++)
@@ -148,7 +156,8 @@ static int add_volume_source(mnl_fields *F, int c, int st, const double wmin0[3]
           cplx A = 1.0;
           if (afunc) {
             double rel[3];
-            for (int d = 0; d < 3; d++) rel[d] = S.has[d] ? p[d] * (0.5 * (1.0 / S.a)) - center[d] : 0.0;
+            for (int d = 0; d < 3; d++)  // loc += shift (src/sources.cpp:270)
+              rel[d] = S.has[d] ? (p[d] + L.shifti[d]) * (0.5 * (1.0 / S.a)) - center[d] : 0.0;
             double re = 0, im = 0;
             afunc(rel, adata, &re, &im);
             A = cplx(re, im);

@@ -69,6 +69,67 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
   return cm.group_end(st);
 }
 
+// step_boundaries over the periodic connections (fields::use_bloch with k = 0; src/boundaries.cpp:
+// 347-623, phase 1): the same kinds and arrays as exchange, with the rank as its own neighbour
+// along every periodic direction -- plane 0 of a component unshifted along it is a copy of plane
+// n, plane n of a shifted one a copy of plane 0.  One launch per call (wrap_kernel); a point on
+// the not-owned planes of several periodic directions maps along all of them at once.  Every
+// component of a kind is listed, whichever way it is shifted, so that whole arrays read back
+// with valid ghosts.  After exchange where both run: the slab ghost planes wrap too.
+// kind WRAP_ALL: every field and polarization array (readers, checkpoints).
+int wrap(mnl_fields *F, int kind, hipStream_t st) {
+  if (!any_periodic(F)) return 0;
+  if (!st) st = F->stream;
+  const DevGrid &g = F->g;
+  const DevFields &f = F->f;
+  WrapArgs w{};
+  for (int k = 0; k < 3; k++) w.N[k] = g.N[k], w.st[k] = g.st[k];
+  for (int d = 0; d < 3; d++)
+    if (g.ax[d] >= 0 && F->periodic[d]) w.per[g.ax[d]] = 1;
+  bool full = false;
+  auto add = [&](double *p, int type, int c) {
+    if (!p) return;
+    for (int i = 0; i < w.n; i++)
+      if (w.a[i].p == p) return;  // H aliasing B, unfused Bn == B
+    if (w.n == WRAP_MAXA) {
+      full = true;
+      return;
+    }
+    int sh = 0;
+    for (int d = 0; d < 3; d++)
+      if (g.ax[d] >= 0 && F->S.shift(3 * type + c, d)) sh |= 1 << g.ax[d];
+    w.a[w.n++] = WrapArr{p, sh};
+  };
+  const bool all = kind == WRAP_ALL;
+  for (int c = 0; c < 3; c++) {
+    if ((kind == 0 || kind == 4 || all) && F->allocated[3 * T_E + c]) {
+      add(f.E[c], T_E, c);
+      if (kind != 0) add(f.WE[c], T_E, c);
+    }
+    if ((kind == 1 || all) && F->allocated[3 * T_H + c]) add(f.Bn[c], T_H, c), add(f.Hn[c], T_H, c);
+    if ((kind == 3 || all) && F->allocated[3 * T_H + c]) add(f.B[c], T_H, c), add(f.H[c], T_H, c);
+    if (((kind == 3 && F->dft_samples_d) || all) && F->allocated[3 * T_D + c]) add(f.D[c], T_D, c);
+    if ((kind == 2 || all) && F->allocated[3 * T_D + c]) {
+      add(f.Dn[c], T_D, c);
+      for (int k = 0; k < f.npol; k++) add(f.pol[k].P[c], T_E, c);
+    }
+  }
+  if (full) return fail("periodic wrap: too many arrays");
+  if (w.n == 0) return 0;
+  wrap_plan(w);
+  if (k_wrap(w, st)) return fail("periodic wrap launch failed");
+  return 0;
+}
+
+// Before whole arrays are read: every ghost plane valid.  In the fused mode the owner of a
+// ghost E point may be implicit (chi1inv * D, not stored), so the mode is left first, which
+// materialises E; the next batch enters it again.
+int wrap_for_readers(mnl_fields *F) {
+  if (!any_periodic(F)) return 0;
+  if (F->fused && set_fused(F, false)) return -1;
+  return wrap(F, WRAP_ALL);
+}
+
 int fused_fail(const char *what, int kr) {
   return fail(std::string(what) + " (" + std::to_string(kr) + ", " +
               hipGetErrorString(hipGetLastError()) + ")");
@@ -478,6 +539,7 @@ static int post_step(mnl_fields *F, PhaseTimer &pt, int s, int cstate = -1) {
       return fail("E halo exchange failed");
     if (exchange(F, 3)) return fail("DFT halo exchange failed");
   }
+  if (wrap(F, 0) || wrap(F, 3)) return -1;  // periodic directions: the same ghosts
   const int k = pt.begin(TM_DFT);
   const int r = dft_update(F, tn, nullptr, cstate);
   pt.end(k);
@@ -548,6 +610,11 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
     if (exchange(F, 0)) return fail("E halo exchange failed");
     pt.end(k);
   }
+  if (any_periodic(F)) {  // step_boundaries(E_stuff) of the step before, at its first reader
+    int k = pt.begin(TM_HALO);
+    if (wrap(F, 0)) return -1;
+    pt.end(k);
+  }
   const BoxList *sl = F->fused ? &F->fused_shell : &F->shell_list;
   int k = pt.begin(TM_BINT);
   bool nr_done = false;  // the NR box's E phase already launched (beside the tile kernel)
@@ -579,6 +646,11 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
     if (exchange(F, 1)) return fail("H halo exchange failed");
     pt.end(kk);
   }
+  if (any_periodic(F)) {
+    int kk = pt.begin(TM_HALO);
+    if (wrap(F, 1)) return -1;
+    pt.end(kk);
+  }
   // ---- D
   if (!F->u_first_done[1] && u_lazy_copy(F, 1)) return -1;
   k = !F->fused ? pt.begin(TM_DINT) : -1;
@@ -596,6 +668,7 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
   if ((F->nr || F->upnl) && F->nranks > 1) {
     if (exchange(F, 2)) return fail("D halo exchange failed");
   }
+  if ((F->nr || F->upnl) && wrap(F, 2)) return -1;
   // ---- E (+ Lorentzian P)
   if (!F->e_first_done && e_lazy_copy(F)) return -1;
   if (F->fused && F->nr) {  // one rank: the fused kernels did all but the NR box
@@ -630,6 +703,7 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
       return fail("wall W launch failed");
     if (f.aniso && F->nranks > 1 && exchange(F, 4))  // WE_stuff ghosts (step.cpp:111-114)
       return fail("W halo exchange failed");
+    if (f.aniso && wrap(F, 4)) return -1;
     if (!fuse && f.npol) {
       if (k_update_pols(F->interior, nullptr, g, f, F->stream) ||
           k_update_pols(F->interior, sl, g, f, F->stream))

@@ -666,7 +666,7 @@ int tb_usable(mnl_fields *F, bool *ok) {
   const bool pol_ok = F->f.npol > 0 && F->fgeo.ngen > 0 && F->nranks == 1 && F->tb_pol_on;
   bool local = F->tb_enabled && F->fused &&
                ((F->fgeo.ngen == 0 && F->f.npol == 0) || pol_ok) && !F->nr && !F->upnl &&
-               F->S.dim == 3 && F->slab_dir == 2;
+               F->S.dim == 3 && F->slab_dir == 2 && !any_periodic(F);
   if (local && tb_plan(F)) return -1;
   if (local && F->tb_have && tb_mid_alloc(F)) local = false;
   if (F->tb_stats && !(local && F->tb_have))

@@ -965,13 +965,15 @@ class Simulation:
         self.eps_averaging = eps_averaging
         self.subpixel_tol = float(kwargs.pop("subpixel_tol", 1e-4))
         self.subpixel_maxeval = int(kwargs.pop("subpixel_maxeval", 100000))
-        if force_complex_fields or k_point or symmetries:
-            raise NotImplementedError("complex fields / Bloch k_point / symmetries are out of scope")
+        if force_complex_fields or symmetries:
+            raise NotImplementedError("complex fields / symmetries are out of scope")
         if dimensions is None:
             dimensions = 3 if self.cell_size.z != 0 else 2
             if self.cell_size.x == 0 and self.cell_size.y == 0:
                 dimensions = 1
         self.dimensions = dimensions
+        self.k_point = k_point
+        self.periodic_directions = self._periodic_directions()
         self.parallel = parallel
         # "upstream": Meep's Pade chi2/chi3 E update instead of the fork's (an
         # extension; the fork's behaviour is the default)
@@ -985,6 +987,34 @@ class Simulation:
         self.fields = None
         self.structure = None
         self.dft_objects = []
+
+    def _periodic_directions(self):
+        """k_point=False: metal walls as before.  A zero Vector3 (Python Meep keeps real fields
+        for it) makes every direction of the cell without a PML periodic
+        (fields::use_bloch(d, 0)); a direction with a PML on both sides keeps its walls behind
+        the PML."""
+        if self.k_point is False or self.k_point is None:
+            return ()
+        if Vector3(*self.k_point) != Vector3():
+            raise NotImplementedError(
+                "a non-zero k_point needs complex fields, which are out of scope "
+                "(k_point=Vector3() gives periodic boundaries with real fields)")
+        if self.dimensions == 1:
+            raise RuntimeError("meep: use_bloch: periodic boundaries of 1-D cells are not "
+                               "supported")
+        out = []
+        for d in ((0, 1) if self.dimensions == 2 else (0, 1, 2)):
+            sides = set()
+            for layer in self.boundary_layers:
+                if isinstance(layer, PML) and layer.direction in (ALL, d):
+                    sides |= {0, 1} if layer.side == ALL else {layer.side}
+            if len(sides) == 1:
+                raise RuntimeError("meep: use_bloch: a PML along a periodic direction is not "
+                                   "supported (direction %s has a PML on one side only)"
+                                   % "XYZ"[d])
+            if not sides:
+                out.append(d)
+        return tuple(out)
 
     # -- structure
     def _create_grid_volume(self):
@@ -1183,6 +1213,8 @@ class Simulation:
             self.fields = core.Fields(self.structure)
         # per-phase GPU times for print_times (HIP events; ~0.3 % of a step)
         self.fields.set_profiling(self.time_phases)
+        for d in self.periodic_directions:  # before the sources: their image chunks
+            self.fields.use_bloch(d)
         for src in self.sources:
             src.add_source(self.fields)
         if getattr(self, "load_fields_file", None):  # delayed load (python/simulation.py:2509-2510)
