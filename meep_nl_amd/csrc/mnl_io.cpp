@@ -848,6 +848,10 @@ std::vector<EBox> energy_boxes(mnl_fields *F, int c, const double wmin[3], const
   else
     yd[0] = 0, yd[1] = 1, yd[2] = 2;
   std::vector<EBox> out;
+  // the lattice shifts outermost (src/loop_in_chunks.cpp:390-532): a region that reaches a
+  // periodic face gets the image chunks whose owned points hold its not-owned planes
+  LatticeShifts ls(S, F->periodic, wmin, wmax);
+  do {
   for (auto &ch : reference_chunks(S)) {
     int isc[3], iec[3];
     double s0c[3], s1c[3], e0c[3], e1c[3];
@@ -861,23 +865,24 @@ std::vector<EBox> energy_boxes(mnl_fields *F, int c, const double wmin[3], const
       const int sh = S.shift(c, d);
       const int uoc = S.io[d] + 2 - sh, coc = ch[d] + 2 - sh, cbo = ch[d] + 2 * ch[3 + d] - sh;
       const int iscoS = std::max(uoc, std::min(coc, cbo)), iecoS = std::max(coc, cbo);
-      isc[d] = std::max(is[d], iscoS);
-      iec[d] = std::min(ie[d], iecoS);
+      isc[d] = std::max(is[d] - ls.shifti[d], iscoS);
+      iec[d] = std::min(ie[d] - ls.shifti[d], iecoS);
       if (isc[d] > iec[d]) emp = true;
     }
     if (emp) continue;
     for (int d = 0; d < 3; d++) {
       if (!S.has[d]) continue;
-      if (isc[d] == is[d]) {
+      const int iscS = isc[d] + ls.shifti[d], iecS = iec[d] + ls.shifti[d];
+      if (iscS == is[d]) {
         s0c[d] = s0[d];
         s1c[d] = s1[d];
-      } else if (isc[d] == is[d] + 2) {
+      } else if (iscS == is[d] + 2) {
         s0c[d] = s1[d];
       }
-      if (iec[d] == ie[d]) {
+      if (iecS == ie[d]) {
         e0c[d] = e0[d];
         e1c[d] = e1[d];
-      } else if (iec[d] == ie[d] - 2) {
+      } else if (iecS == ie[d] - 2) {
         e0c[d] = e1[d];
       }
       if (iec[d] == isc[d]) {
@@ -922,6 +927,7 @@ std::vector<EBox> energy_boxes(mnl_fields *F, int c, const double wmin[3], const
     if (!none) out.push_back(b);
     else out.push_back(EBox{{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {yd[0], yd[1], yd[2]}, dV0});
   }
+  } while (ls.next());
   return out;
 }
 

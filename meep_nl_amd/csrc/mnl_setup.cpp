@@ -99,6 +99,11 @@ static int build_pml_tables(mnl_fields *F) {
         }
       }
       if (flag) F->pml_any[d] = true;
+      // The cell's not-owned plane 0 lies in the first chunk's arrays.  Nothing steps it, but
+      // whoever reads a component there (the centred DFT average beside a low wall, get_field)
+      // must pick the chunk's separate H as at the chunk's owned points: the two differ once
+      // initialize_field has added to B after the first H update copied it.
+      if (flag && z.c0 == 0) F->h_flag[d][0] = 1;
     }
   }
   return 0;

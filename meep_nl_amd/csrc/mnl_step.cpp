@@ -77,6 +77,10 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
 // component of a kind is listed, whichever way it is shifted, so that whole arrays read back
 // with valid ghosts.  After exchange where both run: the slab ghost planes wrap too.
 // kind WRAP_ALL: every field and polarization array (readers, checkpoints).
+// The longest list: E, f_w, B, H, D with the ping-pong sets of B, H and D (24 arrays) and three
+// per susceptibility, of which a structure takes MAX_POL -- one launch holds them all.
+constexpr int WRAP_FIELD_ARRAYS = 3 * 8;  // per direction: E, f_w, Bn, Hn, B, H, D, Dn (the add() calls below)
+static_assert(WRAP_FIELD_ARRAYS + 3 * MAX_POL <= WRAP_MAXA, "wrap(WRAP_ALL) must fit one launch");
 int wrap(mnl_fields *F, int kind, hipStream_t st) {
   if (!any_periodic(F)) return 0;
   if (!st) st = F->stream;
@@ -91,7 +95,7 @@ int wrap(mnl_fields *F, int kind, hipStream_t st) {
     if (!p) return;
     for (int i = 0; i < w.n; i++)
       if (w.a[i].p == p) return;  // H aliasing B, unfused Bn == B
-    if (w.n == WRAP_MAXA) {
+    if (w.n == WRAP_MAXA) {  // out of reach (the static_assert above); it guards w.a all the same
       full = true;
       return;
     }

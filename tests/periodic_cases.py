@@ -32,6 +32,7 @@ CASES = {
     4: dict(dim=3, n=(24, 20, 32), per=(0, 1), pml=(2,)),      # the metasurface cell
     5: dict(dim=3, n=(16, 14, 18), per=(0, 1, 2), pml=()),     # all three
     "2d": dict(dim=2, n=(20, 18, 0), per=(0,), pml=(1,)),      # x periodic, y PML
+    "2dy": dict(dim=2, n=(19, 22, 0), per=(1,), pml=(0,)),     # y periodic, x PML
 }
 # families whose E update reads neighbouring components: reach 2 per step
 REACH2 = ("nr", "upstream", "aniso")
@@ -39,12 +40,17 @@ FAMILIES = ("plain", "lorentz", "nr", "upstream", "aniso", "cond", "mu")
 
 
 def reach(family):
-    return 2 if family in REACH2 else 1
+    return 2 if any(f in REACH2 for f in family.split("+")) else 1
+
+
+def case_of(case):
+    """A key of CASES, or a dict of the same form (the random family draws its own cells)."""
+    return case if isinstance(case, dict) else CASES[case]
 
 
 def steps_bound(case, R, family):
     """The largest T with s * T <= m - 2, m the cells from the central replica to the wall."""
-    c = CASES[case]
+    c = case_of(case)
     m = min((R - 1) // 2 * c["n"][d] for d in c["per"])
     return (m - 2) // reach(family)
 
@@ -86,7 +92,7 @@ class Scene:
     (R = 1: the periodic product run itself)."""
 
     def __init__(self, case, family, R, trans=(0, 0, 0), planar_comp=0):
-        c = CASES[case]
+        c = case_of(case)
         self.case, self.family, self.R = case, family, R
         self.trans = tuple(trans)  # everything moved cyclically by so many cells (periodic axes)
         # the planar source's component.  Ex is shifted along x: where x is periodic its end
@@ -95,7 +101,7 @@ class Scene:
         # so the replication property holds bit for bit only for a component unshifted along
         # the periodic axes (1/2 + 1/2)
         self.planar_comp = planar_comp
-        self.dim, self.n, self.per, self.pml = c["dim"], c["n"], c["per"], c["pml"]
+        self.dim, self.n, self.per, self.pml = c["dim"], tuple(c["n"]), tuple(c["per"]), c.get("pml", ())
         self.k = (R - 1) // 2
         self.n_super = [self.n[d] * (R if d in self.per else 1) for d in range(3)]
         # the central replica sits at the same coordinates as the periodic cell [0, L]
@@ -137,6 +143,47 @@ class Scene:
         return arr[tuple(sl)]
 
 
+def materials(o, sc, block, slab):
+    """The family's materials (sc.family; several joined with "+") with the dielectric block
+    and the slab as masks over the cell's (n + 1)-point axes."""
+    fams = sc.family.split("+")
+    ecomps = E_COMPS
+    if "upstream" in fams:
+        o.set_upstream_nl(True)
+    for c in ecomps:
+        o.set_chi1inv(c, c, sc.tile(np.where(block, 0.25, 1.0)))
+        if ("nr" in fams or "upstream" in fams):
+            for d in range(3):
+                if d != c:
+                    o.set_chi1inv(c, d, sc.tile(np.where(block, 1e-3, 0.0)))
+        if "nr" in fams:
+            o.set_chi2(c, sc.tile(np.where(block, 0.5, 0.0)))
+        if "upstream" in fams:
+            o.set_chi3(c, sc.tile(np.where(block, 2e-2, 0.0)))
+            o.set_chi2(c, sc.tile(np.where(block, 3e-2, 0.0)))
+    # (above the sources' planes: a D source inside a polarization box keeps a run unfused)
+    if "lorentz" in fams:
+        o.add_lorentzian(1.1, 0.05, [sc.tile(np.where(slab, 0.6, 0.0)) for _ in ecomps])
+    if "lorentz4" in fams:  # as many terms as a structure takes: 12 polarization arrays to wrap
+        for k in range(4):
+            o.add_lorentzian(0.7 + 0.1 * k, 0.05 + 0.01 * k,
+                             [sc.tile(np.where(slab, 0.1 + 0.05 * k, 0.0)) for _ in ecomps])
+    if "aniso" in fams:
+        sig = [[None] * 3 for _ in range(3)]
+        for c in ecomps:
+            sig[c][c] = sc.tile(np.where(slab, 0.4, 0.0))
+        sig[0][1] = sc.tile(np.where(slab, 0.1, 0.0))
+        sig[1][0] = sc.tile(np.where(slab, 0.1, 0.0))
+        o.add_lorentzian_tensor(1.0, 0.05, sig)
+    if "cond" in fams:
+        for c in D_COMPS + B_COMPS:
+            o.set_conductivity(c, sc.tile(np.where(slab, 0.7, 0.0)))
+    if "mu" in fams:
+        for c in H_COMPS:
+            o.set_chi1inv(c, c % 3, sc.tile(np.where(block, 1 / 2.5, 1.0)))
+        o.add_magnetic_lorentzian(1.0, 0.1, [sc.tile(np.where(slab, 0.3, 0.0)) for _ in H_COMPS])
+
+
 def configure(o, sc, seed=11, init=True):
     """The same content on a periodic cell (sc.R == 1, o periodic already) or its supercell:
     PML on the non-periodic axes, a dielectric block across the seam, the family's materials, a
@@ -145,39 +192,7 @@ def configure(o, sc, seed=11, init=True):
     fam, dim = sc.family, sc.dim
     if sc.pml:
         o.add_pml(PML_CELLS / A, dirs=tuple(sc.pml))
-    block = sc.mask()
-    ecomps = E_COMPS
-    if fam == "upstream":
-        o.set_upstream_nl(True)
-    for c in ecomps:
-        o.set_chi1inv(c, c, sc.tile(np.where(block, 0.25, 1.0)))
-        if fam in ("nr", "upstream"):
-            for d in range(3):
-                if d != c:
-                    o.set_chi1inv(c, d, sc.tile(np.where(block, 1e-3, 0.0)))
-        if fam == "nr":
-            o.set_chi2(c, sc.tile(np.where(block, 0.5, 0.0)))
-        if fam == "upstream":
-            o.set_chi3(c, sc.tile(np.where(block, 2e-2, 0.0)))
-            o.set_chi2(c, sc.tile(np.where(block, 3e-2, 0.0)))
-    # (above the sources' planes: a D source inside a polarization box keeps a run unfused)
-    slab = sc.mask(0.6, 0.85, seam=2)
-    if fam == "lorentz":
-        o.add_lorentzian(1.1, 0.05, [sc.tile(np.where(slab, 0.6, 0.0)) for _ in ecomps])
-    if fam == "aniso":
-        sig = [[None] * 3 for _ in range(3)]
-        for c in ecomps:
-            sig[c][c] = sc.tile(np.where(slab, 0.4, 0.0))
-        sig[0][1] = sc.tile(np.where(slab, 0.1, 0.0))
-        sig[1][0] = sc.tile(np.where(slab, 0.1, 0.0))
-        o.add_lorentzian_tensor(1.0, 0.05, sig)
-    if fam == "cond":
-        for c in D_COMPS + B_COMPS:
-            o.set_conductivity(c, sc.tile(np.where(slab, 0.7, 0.0)))
-    if fam == "mu":
-        for c in H_COMPS:
-            o.set_chi1inv(c, c % 3, sc.tile(np.where(block, 1 / 2.5, 1.0)))
-        o.add_magnetic_lorentzian(1.0, 0.1, [sc.tile(np.where(slab, 0.3, 0.0)) for _ in H_COMPS])
+    materials(o, sc, sc.mask(), sc.mask(0.6, 0.85, seam=2))
     if hasattr(o, "make_periodic"):  # the product: fields::use_bloch before the sources
         o.make_periodic(sc.per)
     # sources: every replica gets its own copy (the periodic run: one, with its image chunks)

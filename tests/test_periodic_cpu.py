@@ -10,12 +10,16 @@ import numpy as np
 import pytest
 
 import periodic_cases as pc
+import periodic_fuzz as pf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # every (case, family) the GPU file uses, with its step count
 GPU_CONFIGS = [(1, "plain"), (2, "plain"), (3, "plain"), (4, "plain"), (5, "plain"),
                ("2d", "plain")] + [(4, f) for f in pc.FAMILIES if f != "plain"]
+# and tests/test_gpu_periodic_monitors.py
+GPU_CONFIGS += [(4, "lorentz4"), ("2dy", "plain"), ("2dy", "lorentz")] + \
+    [(c, f) for c in (5, "2dy") for f in pc.REACH2]
 
 
 def test_steps_bound_is_the_stated_condition():
@@ -40,6 +44,82 @@ def test_light_cone_bound_on_the_oracle(case, family):
         assert np.array_equal(a, b), (case, family, c, float(np.max(np.abs(a - b))))
         nonzero += bool(np.any(a != 0))
     assert nonzero == 12
+
+
+ALL_SEEDS = [(r, s) for r in (1, 2, 3) for s in pf.SEEDS[r]]
+
+
+@pytest.mark.parametrize("ranks,seed", ALL_SEEDS)
+def test_light_cone_bound_of_the_random_family(ranks, seed):
+    """Every seed of tests/test_gpu_periodic_fuzz.py: 3 against 5 replicas on the oracle alone,
+    the central replica bitwise equal through the seed's T, all 12 arrays non-zero."""
+    from scenarios import make_oracle
+    cfg = pf.draw(seed, ranks)
+    got = []
+    for R in (3, 5):
+        sc, o, _ = pf.build(make_oracle, cfg, R, monitors=False)
+        o.step(cfg["T"])
+        got.append({c: sc.central(o.get_array(c)).copy() for c in pc.ALL_COMPS})
+    for c in pc.ALL_COMPS:
+        assert np.array_equal(got[0][c], got[1][c]), (seed, c)
+        assert np.any(got[0][c] != 0), (seed, c)
+
+
+def test_draw_is_a_function_of_the_seed():
+    assert pf.draw(7) == pf.draw(7) and pf.draw(7) != pf.draw(8)
+    assert pf.draw(100, 2)["ranks"] == 2 and pf.draw(100, 2) != pf.draw(100, 3)
+
+
+def test_random_family_coverage():
+    """What the committed seed lists cover, counted from draw alone."""
+    one = [pf.draw(s, 1) for s in pf.SEEDS[1]]
+    cfgs = one + [pf.draw(s, r) for r in (2, 3) for s in pf.SEEDS[r]]
+    assert len(one) == 40 and [len(pf.SEEDS[r]) for r in (2, 3)] == [4, 4]
+
+    def count(pred, over=cfgs):
+        return sum(bool(pred(c)) for c in over)
+    for dim, per in pf.SUBSETS:
+        assert count(lambda c: c["dim"] == dim and c["per"] == per) >= (3 if dim == 3 else 2), per
+    for fam in pc.FAMILIES:
+        assert count(lambda c: c["family"] == fam) >= 4, fam
+    for fam in pf.FAMILIES[len(pc.FAMILIES):]:  # the two combinations
+        assert count(lambda c: c["family"] == fam) >= 3, fam
+    # each clause of the fused rule decides the mode of a seed that is otherwise fusable
+    alone = [c for c in one if c["dim"] == 3 and c["family"] in pf.FUSABLE and not c["fused_expected"]]
+    assert any(all(not s["in_pml"] for s in c["sources"]) for c in alone)       # an H source
+    assert any(all(s["comp"] < 3 for s in c["sources"]) for c in alone)         # an E_d in PML
+
+    def on_seam(c):
+        return any(s["kind"] == "point" and any(s["pos"][d] == 0 for d in c["per"])
+                   for s in c["sources"])
+
+    def sides(c):  # per non-periodic axis the set of sides with PML
+        out = {d: set() for d in pc.axes_of(c["dim"]) if d not in c["per"]}
+        for d, s, _ in c["pml"]:
+            out[d].add(s)
+        return out
+
+    def sticks_out(c):
+        return any(s["kind"] == "volume" and any(
+            (s["lo"][d] < 0) != (s["hi"][d] > 2 * c["n"][d]) for d in c["per"])
+            for s in c["sources"])
+    assert count(on_seam) >= 8
+    assert count(lambda c: any(s["comp"] >= 3 for s in c["sources"])) >= 5
+    assert count(lambda c: any(len(v) == 1 for v in sides(c).values())) >= 6
+    assert count(lambda c: any(len(v) < 2 for v in sides(c).values())) >= 4  # a metal wall
+    assert count(lambda c: c["n"][0] > 64) >= 4
+    assert count(lambda c: c["n"][0] % 2 == 0) >= 10  # odd point count (n + 1)
+    assert count(lambda c: c["n"][0] % 2 == 1) >= 10
+    assert count(sticks_out) >= 6
+    assert count(lambda c: c["fused_expected"], one) >= 20
+    # the rules of the product
+    for c in cfgs:
+        assert not any(d in c["per"] for d, _, _ in c["pml"])
+        if pc.reach(c["family"]) == 2:
+            assert len({d for d, _, _ in c["pml"]}) <= 1
+        for d, v in sides(c).items():
+            assert c["n"][d] - sum(t for dd, _, t in c["pml"] if dd == d) >= 6
+        assert all(10 <= c["n"][d] for d in c["per"]) and sum(c["schedule"]) == c["T"] >= 1
 
 
 def test_light_cone_is_sharp_enough_to_matter():
