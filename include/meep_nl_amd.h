@@ -516,6 +516,40 @@ int mnl_fields_dft_scale(mnl_fields *f, int handle, double re, double im);
  * reads the file.  Loading checks the magic, nfreq and the sizes, not the frequencies. */
 int mnl_fields_dft_save(mnl_fields *f, int handle, const char *filename);
 int mnl_fields_dft_load_file(mnl_fields *f, int handle, const char *filename, int sign);
+/* ---- Field probes: fields::get_field(c, pt) (src/monitor.cpp:127-160) after every step ------
+ * A probe records, on the device and inside whatever stepping mode is active, the value
+ * mnl_fields_get_field(comp, pos) would return after each step: the same interpolation points
+ * and weights, the same per-point value rule, added in the same order (bitwise, except that a
+ * -0.0 may read +0.0).  It is sampled with the DFT monitors, so steps are
+ * never split by it.  *handle is a probe handle (not a DFT handle: the DFT data calls refuse it,
+ * and adding a probe moves no DFT handle).  A probe of a component that has no array yet
+ * records 0.  Probes are not part of mnl_fields_dump; after mnl_fields_load or
+ * mnl_fields_set_time a probe is empty at the new step. */
+int mnl_fields_add_probe(mnl_fields *f, int comp, const double pos[3], int *handle);
+/* The values since the last read (or since the probe was added / reset), oldest first:
+ * *count values, the first one that of step *t_first (the state after *t_first steps).  The
+ * series holds the last 65536 steps (MNL_PROBE_CAP when the probe is added); older values are
+ * dropped, which *t_first shows.  values == NULL: only *count and *t_first, nothing is
+ * consumed; otherwise values[cap] with cap >= *count, and the series is emptied.  Buffered
+ * samples are flushed first.  Distributed: collective, every rank gets the sum over the ranks
+ * of their partial sums (fields::get_field(..., parallel = true)). */
+int mnl_fields_probe_read(mnl_fields *f, int handle, long long cap, long long *count,
+                          long long *t_first, double *values);
+/* Empty a probe's series / remove one probe (the other probes keep their handles) / remove
+ * every probe (their handles become invalid). */
+int mnl_fields_probe_reset(mnl_fields *f, int handle);
+int mnl_fields_remove_probe(mnl_fields *f, int handle);
+int mnl_fields_remove_probes(mnl_fields *f);
+/* fields::dft_norm() (src/dft.cpp:312-361): the square root of the sum of |dft|^2 over every
+ * frequency and point of every chunk list of every DFT object (flux, fields, near2far, energy,
+ * force; not probes), reduced on the device in a fixed order and summed over the ranks
+ * (collective).  Buffered updates are accumulated first. */
+int mnl_fields_dft_norm(mnl_fields *f, double *norm);
+/* fields::dft_maxfreq() (src/dft.cpp:380-399): the largest |omega| / 2 pi of any DFT object, 0
+ * without any.  fields::max_decimation() (src/dft.cpp:365-377): the largest decimation factor
+ * in use, at least 1.  Host only. */
+int mnl_fields_dft_maxfreq(mnl_fields *f, double *maxfreq);
+int mnl_fields_max_decimation(mnl_fields *f, int *decimation);
 /* Accumulate every buffered DFT update now and wait for the device (no reference
  * counterpart: the reference adds each update to the DFT array in fields::update_dfts,
  * src/dft.cpp:249-263; this build samples every update and adds up to 32 of them per pass

@@ -12,13 +12,15 @@ from .simulation import (ALL, AUTOMATIC, Block, ContinuousSource, CustomSource, 
                          FluxRegion, GaussianSource, High, LorentzianSusceptibility, Low, Medium,
                          PML, Simulation, Source, Vector3, Volume, after_sources, after_time,
                          air, at_beginning, at_end, at_every, before_time, combine_step_funcs,
-                         during_sources, get_flux_freqs, get_fluxes, get_near2far_freqs, inf, stop_after_walltime,
+                         during_sources, get_flux_freqs, get_fluxes, get_near2far_freqs, inf,
+                         stop_after_walltime,
                          FluxData, NearToFarData, scale_flux_fields, scale_near2far_fields,
                          DftEnergy, DftForce, EnergyRegion, ForceData, ForceRegion,
                          get_electric_energy, get_energy_freqs, get_force_freqs, get_forces,
                          get_magnetic_energy, get_total_energy, scale_energy_fields,
                          scale_force_fields,
-                         stop_when_fields_decayed, vacuum, when_false, when_true, verbosity,
+                         stop_when_fields_decayed, stop_when_energy_decayed,
+                         stop_when_dft_decayed, vacuum, when_false, when_true, verbosity,
                          quiet, wall_time)
 
 __version__ = "0.1.0"

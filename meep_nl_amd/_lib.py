@@ -113,6 +113,14 @@ _SIGS = {
     "mnl_fields_dft_save": (c_int, [c_void, c_int, ctypes.c_char_p]),
     "mnl_fields_dft_load_file": (c_int, [c_void, c_int, ctypes.c_char_p, c_int]),
     "mnl_fields_dft_flush": (c_int, [c_void]),
+    "mnl_fields_add_probe": (c_int, [c_void, c_int, dptr, iptr]),
+    "mnl_fields_probe_read": (c_int, [c_void, c_int, ctypes.c_longlong, llptr, llptr, dptr]),
+    "mnl_fields_probe_reset": (c_int, [c_void, c_int]),
+    "mnl_fields_remove_probe": (c_int, [c_void, c_int]),
+    "mnl_fields_remove_probes": (c_int, [c_void]),
+    "mnl_fields_dft_norm": (c_int, [c_void, dptr]),
+    "mnl_fields_dft_maxfreq": (c_int, [c_void, dptr]),
+    "mnl_fields_max_decimation": (c_int, [c_void, iptr]),
     "mnl_fields_set_time": (c_int, [c_void, ctypes.c_longlong]),
     "mnl_fields_zero_fields": (c_int, [c_void]),
     "mnl_fields_remove_sources": (c_int, [c_void]),

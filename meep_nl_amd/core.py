@@ -734,6 +734,51 @@ class Fields:
         step calls)."""
         check(lib().mnl_fields_dft_flush(self.h))
 
+    # -- field probes and the DFT norm (DESIGN.md section 32)
+    def add_probe(self, comp, pos):
+        """get_field(comp, pos) recorded after every step on the device, in whatever stepping
+        mode is active; returns a probe handle (not a DFT handle)."""
+        pos = np.ascontiguousarray(list(pos) + [0.0] * (3 - len(pos)), dtype=np.float64)
+        h = ctypes.c_int()
+        check(lib().mnl_fields_add_probe(self.h, int(comp), ptr(pos), ctypes.byref(h)))
+        return h.value
+
+    def probe_read(self, h):
+        """(t_first, values): the probe's values since the last read, oldest first, values[k]
+        that of the state after t_first + k steps (collective; summed over the ranks).  Only
+        the last 65536 steps are kept: t_first shows what was dropped."""
+        n, t0 = ctypes.c_longlong(), ctypes.c_longlong()
+        check(lib().mnl_fields_probe_read(self.h, h, 0, ctypes.byref(n), ctypes.byref(t0), None))
+        out = np.zeros(max(n.value, 1), dtype=np.float64)
+        check(lib().mnl_fields_probe_read(self.h, h, out.size, ctypes.byref(n), ctypes.byref(t0),
+                                          ptr(out)))
+        return t0.value, out[:n.value]
+
+    def probe_reset(self, h):
+        check(lib().mnl_fields_probe_reset(self.h, h))
+
+    def remove_probe(self, h):
+        check(lib().mnl_fields_remove_probe(self.h, h))
+
+    def remove_probes(self):
+        check(lib().mnl_fields_remove_probes(self.h))
+
+    def dft_norm(self):
+        """fields::dft_norm(): sqrt of the sum of |dft|^2 over every DFT object (collective)."""
+        v = ctypes.c_double()
+        check(lib().mnl_fields_dft_norm(self.h, ctypes.byref(v)))
+        return v.value
+
+    def dft_maxfreq(self):
+        v = ctypes.c_double()
+        check(lib().mnl_fields_dft_maxfreq(self.h, ctypes.byref(v)))
+        return v.value
+
+    def max_decimation(self):
+        v = ctypes.c_int()
+        check(lib().mnl_fields_max_decimation(self.h, ctypes.byref(v)))
+        return v.value
+
     def dft_decimation(self, h):
         v = ctypes.c_int()
         check(lib().mnl_fields_dft_decimation(self.h, h, ctypes.byref(v)))

@@ -224,7 +224,7 @@ static size_t dft_nchunks(const DftFluxH &o) {
 
 // updates per accumulation of a new monitor: DFT_KB, or MNL_DFT_BLOCK (1 .. DFT_KB), read when
 // the monitor is added
-static int dft_block() {
+int dft_block() {
   const char *e = getenv("MNL_DFT_BLOCK");
   return e ? std::max(1, std::min(DFT_KB, atoi(e))) : DFT_KB;
 }
@@ -348,6 +348,7 @@ int dft_layout(mnl_fields *F, std::unique_ptr<DftFluxH> &o, DftFluxH &ho, std::v
     HIPCHK(hipStreamSynchronize(F->stream));
   }
   F->dfts.push_back(std::move(o));
+  dft_sampled_rebuild(F);
   return int(F->dfts.size()) - 1;
 }
 
@@ -576,7 +577,7 @@ static int dft_pair_sum(mnl_fields *F, DftFluxH &o, int s, double *out) {
 
 // dft_energy::electric / magnetic / total (src/dft.cpp:657-699): which 0, 1, 2
 int dft_energy_values(mnl_fields *F, int h, int which, double *out) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (o.kind != DFT_ENERGY) return fail("dft_energy: the handle is not an energy object");
   if (which < 0 || which > 2)
@@ -590,7 +591,7 @@ int dft_energy_values(mnl_fields *F, int h, int which, double *out) {
 
 // dft_force::force (src/stress.cpp:101-114)
 int dft_force_values(mnl_fields *F, int h, double *out) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (o.kind != DFT_FORCE) return fail("dft_force: the handle is not a force object");
   return dft_pair_sum(F, o, 0, out);
@@ -600,7 +601,7 @@ int dft_force_values(mnl_fields *F, int h, double *out) {
 // component, and the loop weight as update_dft applies it (after the square root; 1.0 for
 // unweighted lists).  Recomputed from the chunks' loops, not stored.
 int dft_points(mnl_fields *F, int h, int which, double *out, long long npoints) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   const DftFluxH &o = *F->dfts[h];
   if (dft_bad_which(o, which)) return fail("dft_points: no such list");
   const mnl_structure &S = F->S;
@@ -756,7 +757,7 @@ int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const doubl
 
 // per point of the list (the order of mnl_fields_dft_data): x, y, z, c0, weight
 int n2f_points(mnl_fields *F, int h, double *out, long long npoints) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   const DftFluxH &o = *F->dfts[h];
   if (!o.n2f) return fail("near2far_points: the handle is not a near2far object");
   long long k = 0;
@@ -774,7 +775,7 @@ int n2f_points(mnl_fields *F, int h, double *out, long long npoints) {
 // out[npts][nfreq][6] complex.  Far points go through the kernels in batches that fit the
 // scratch buffer of partial sums; the batching does not change any point's result.
 int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (!o.n2f) return fail("near2far_farfields: the handle is not a near2far object");
   if (npts < 0) return fail("near2far_farfields: negative point count");
@@ -854,7 +855,7 @@ int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, doubl
 // the rows of the updates still buffered from earlier calls (accumulated by the next flush:
 // when kb updates are buffered or before the DFT array is read, not at the end of every call)
 int dft_prepare(mnl_fields *F, long long t0, int ns) {
-  for (auto &op : F->dfts) {
+  for (auto &op : F->dfts) {  // (probes have no phases)
     DftFluxH &o = *op;
     const size_t nch = dft_nchunks(o);
     const size_t rowlen = 2 * nch * (size_t)o.nfreq;
@@ -926,6 +927,7 @@ int dft_prepare(mnl_fields *F, long long t0, int ns) {
 // accumulate the buffered updates of one flux object
 int dft_flush(mnl_fields *F, DftFluxH &o) {
   if (!o.nbuf) return 0;
+  if (o.kind == DFT_PROBE) return probe_flush(F, o);
   const size_t nch = dft_nchunks(o);
   const long long rstride = (long long)(nch * o.nfreq);
   if (k_dft_accum(o.d_pj, o.d_pch, o.d_dft, o.d_fr, o.nbuf,
@@ -960,7 +962,7 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
     J = DftSampleJobs{};
     return 0;
   };
-  for (auto &op : F->dfts) {
+  for (DftFluxH *op : F->sampled) {
     DftFluxH &o = *op;
     if (t % o.decim || !o.npts) continue;
     double *fr = o.d_fr + (size_t)o.nbuf * o.npts;
@@ -1012,7 +1014,7 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
     }
   }
   if (launch()) return -1;
-  for (auto &op : F->dfts) {
+  for (DftFluxH *op : F->sampled) {
     DftFluxH &o = *op;
     if (t % o.decim || !o.npts) continue;
     o.nbuf++;
@@ -1023,14 +1025,14 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
 }
 
 bool dft_due(const mnl_fields *F, long long t) {
-  for (auto &op : F->dfts)
+  for (DftFluxH *op : F->sampled)
     if (op->npts && t % op->decim == 0) return true;
   return false;
 }
 
 
 int dft_flux_values(mnl_fields *F, int h, double *out) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (dft_flush(F, o)) return -1;  // the buffered updates first
   const size_t nf = o.nfreq;
@@ -1070,7 +1072,7 @@ int dft_flux_values(mnl_fields *F, int h, double *out) {
 // collapse_array (src/array_slice.cpp:554-601).  out: re/im interleaved.
 int dft_array(mnl_fields *F, int h, int c, int num_freq, int *rank, long long dims[3], double *out,
               long long nout) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (o.kind == DFT_ENERGY || o.kind == DFT_FORCE)
     return fail("get_dft_array: not available for energy and force objects in this build");
@@ -1249,7 +1251,7 @@ static int dft_io_timed(mnl_fields *F, int id, double bytes, Fn launch) {
 }
 
 int dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (dft_bad_which(o, which)) return fail("dft_get: which must be 0 (E) or 1 (H)");
   const size_t nl = dft_list_points(o, which) * (size_t)o.nfreq;  // complex values
@@ -1270,7 +1272,7 @@ int dft_get(mnl_fields *F, int h, int which, double *out, long long n) {
 }
 
 int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   if (sign != 1 && sign != -1) return fail("dft_load: sign must be 1 or -1");
   DftFluxH &o = *F->dfts[h];
   if (dft_bad_which(o, which)) return fail("dft_load: which must be 0 (E) or 1 (H)");
@@ -1295,7 +1297,7 @@ int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int
 }
 
 int dft_scale(mnl_fields *F, int h, double re, double im) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   if (dft_flush(F, o)) return -1;  // everything accumulated so far is scaled
   const size_t nc = ((o.npts + 63) & ~size_t(63)) * (size_t)o.nfreq;

@@ -507,6 +507,7 @@ int mnl_fields_time(mnl_fields *F, long long *t, double *dt) {
 int mnl_fields_set_time(mnl_fields *F, long long t) {
   if (!F || t < 0) return fail("bad argument");
   F->t = t;
+  probe_restart(F);
   return 0;
 }
 
@@ -648,7 +649,7 @@ int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
   }
   if (F->t != 0 || F->e_first_done || F->h_first_done || F->u_first_done[0] || F->u_first_done[1])
     return fail("use_bloch: only before the first step");
-  if (!F->groups.empty() || !F->dfts.empty())
+  if (!F->groups.empty() || !F->sampled.empty())
     return fail("use_bloch: only before sources and DFT monitors are added");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   if (F->fused && set_fused(F, false)) return -1;
@@ -699,7 +700,7 @@ int mnl_fields_set_schedule(mnl_fields *F, int which, int value) {
     else
       F->*o.flag = value != 0;
     if (which == MNL_SCHED_DFT_PAL)  // the sampling plans are rebuilt at the next update
-      for (auto &d : F->dfts) d->plan_key = -1;
+      for (DftFluxH *d : F->sampled) d->plan_key = -1;
     if (which == MNL_SCHED_TB_OX) F->tb_ox_set = value != 0;  // the tuner keeps a set width
     if (o.replan) F->tb_sig = 0;  // the pair plan is rebuilt at the next batch
     return 0;
@@ -759,7 +760,7 @@ int mnl_fields_dft_flux(mnl_fields *F, int h, double *out) {
 
 int mnl_fields_dft_size(mnl_fields *F, int h, long long *n) {
   if (!F || !n) return fail("null argument");
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   const DftFluxH &o = *F->dfts[h];
   long long k = 0;
   for (auto &dc : o.E) k += (long long)dc.N;
@@ -777,7 +778,7 @@ int mnl_fields_dft_flush(mnl_fields *F) {
 
 int mnl_fields_dft_data(mnl_fields *F, int h, int which, double *out, long long n) {
   if (!F || !out) return fail("null argument");
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   if (dft_flush(F, *F->dfts[h])) return -1;  // the buffered updates first
   const DftFluxH &o = *F->dfts[h];
   const size_t nf = o.nfreq;
@@ -828,9 +829,63 @@ int mnl_fields_dft_load_file(mnl_fields *F, int h, const char *filename, int sig
   return dft_load_file(F, h, filename, sign);
 }
 
+int mnl_fields_add_probe(mnl_fields *F, int comp, const double pos[3], int *handle) {
+  if (!F || !pos || !handle) return fail("null argument");
+  if (check_comp(comp)) return -1;
+  if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  const int h = probe_add(F, comp, pos);
+  if (h < 0) return -1;
+  *handle = h;
+  return 0;
+}
+
+int mnl_fields_probe_read(mnl_fields *F, int h, long long cap, long long *count,
+                          long long *t_first, double *values) {
+  if (!F || !count || !t_first) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return probe_read(F, h, cap, count, t_first, values);
+}
+
+int mnl_fields_probe_reset(mnl_fields *F, int h) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return probe_reset(F, h);
+}
+
+int mnl_fields_remove_probe(mnl_fields *F, int h) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return probe_remove(F, h);
+}
+
+int mnl_fields_remove_probes(mnl_fields *F) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return probe_remove_all(F);
+}
+
+int mnl_fields_dft_norm(mnl_fields *F, double *norm) {
+  if (!F || !norm) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return dft_norm(F, norm);
+}
+
+int mnl_fields_dft_maxfreq(mnl_fields *F, double *maxfreq) {
+  if (!F || !maxfreq) return fail("null argument");
+  *maxfreq = dft_maxfreq(F);
+  return 0;
+}
+
+int mnl_fields_max_decimation(mnl_fields *F, int *decimation) {
+  if (!F || !decimation) return fail("null argument");
+  *decimation = dft_max_decimation(F);
+  return 0;
+}
+
 int mnl_fields_dft_decimation(mnl_fields *F, int h, int *decimation) {
   if (!F || !decimation) return fail("null argument");
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   *decimation = F->dfts[h]->decim;
   return 0;
 }
@@ -858,7 +913,7 @@ int mnl_fields_near2far_farfields(mnl_fields *F, int h, long long npts, const do
 
 int mnl_fields_near2far_medium(mnl_fields *F, int h, double *eps, double *mu) {
   if (!F || !eps || !mu) return fail("null argument");
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   if (!F->dfts[h]->n2f) return fail("near2far_medium: the handle is not a near2far object");
   *eps = F->dfts[h]->eps;
   *mu = F->dfts[h]->mu;
@@ -911,7 +966,7 @@ int mnl_fields_dft_points(mnl_fields *F, int h, int which, double *out, long lon
 
 int mnl_fields_dft_list_size(mnl_fields *F, int h, int which, long long *n) {
   if (!F || !n) return fail("null argument");
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   const DftFluxH &o = *F->dfts[h];
   if (dft_bad_which(o, which)) return fail("dft_list_size: no such list");
   *n = (long long)dft_list_points(o, which) * o.nfreq;

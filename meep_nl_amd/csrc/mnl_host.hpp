@@ -210,7 +210,7 @@ struct DftChunkH {
   int shifti[3] = {0, 0, 0};  // periodic image chunk: the lattice shift from a loop point to
                               // the point of the region it stands for (dft_chunk::shift)
 };
-enum { DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4 };
+enum { DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4, DFT_PROBE = 5 };
 constexpr int DFT_MAXLISTS = 4;
 struct DftFluxH {
   std::vector<double> omega;
@@ -284,6 +284,20 @@ struct DftFluxH {
   } ps[2];
   double *d_ps_part = nullptr, *d_ps_out = nullptr;
   size_t ps_part_cap = 0;
+  // the fixed split of dft_norm's sum over the padded array into workgroups, its partial sums
+  // [workgroup] and the result
+  int norm_nwg = 0;
+  long long norm_wg_blocks = 0;
+  double *d_norm_part = nullptr;
+  // field probe (kind DFT_PROBE): one list of up to 8 points with the
+  // get_field weights, no frequencies.  Its flush turns each buffered row into one value of
+  // the device series, a ring of series_cap values: the last series_n steps up to series_t
+  // (the oldest dropped on overrun), the value of step s at index s % series_cap.  The probe
+  // owns its device arrays (freed with it; those of the other kinds live as long as the fields).
+  double *d_series = nullptr;
+  int *d_pslot = nullptr;             // the points' slots in list order (-1: another rank's)
+  int series_cap = 0;
+  long long series_n = 0, series_t = 0;
   DftFluxH() = default;
   DftFluxH(const DftFluxH &) = delete;
   ~DftFluxH() {
@@ -292,8 +306,11 @@ struct DftFluxH {
                     (void *)d_ps_out, (void *)d_list, (void *)d_n2f_part,
                     (void *)d_n2f_xyz, (void *)d_n2f_out, (void *)d_ph, (void *)d_sidx,
                     (void *)d_ssel, (void *)d_spal, d_su, (void *)d_bad, (void *)d_cmp,
-                    (void *)d_sci})
+                    (void *)d_sci, (void *)d_norm_part, (void *)d_series, (void *)d_pslot})
       if (p) (void)hipFree(p);
+    if (kind == DFT_PROBE)
+      for (void *p : {(void *)d_pj, (void *)d_pch, (void *)d_pw, (void *)d_ch, (void *)d_fr})
+        if (p) (void)hipFree(p);
   }
 };
 
@@ -518,12 +535,19 @@ struct mnl_fields {
   size_t scratch_cap = 0;
   std::vector<std::unique_ptr<DftFluxH>> dfts;  // DFT flux objects (add_dft_flux order)
   bool dft_samples_d = false;  // a monitor samples a D component (its low ghost: exchange 3)
+  // field probes (mnl_probe.cpp): their own list, so that no DFT handle moves; a removed probe
+  // leaves an empty entry.  sampled: what every step samples -- the DFT objects, then the probes
+  std::vector<std::unique_ptr<DftFluxH>> probes;
+  std::vector<DftFluxH *> sampled;
+  double *d_norm_out = nullptr;  // dft_norm's per-object sums
+  size_t norm_out_cap = 0;
 
   ~mnl_fields() {
     if (device >= 0) hipSetDevice(device);
     for (void *p : dev_allocs) hipFree(p);
     for (auto e : ev_pool) hipEventDestroy(e);
     if (d_scratch) hipFree(d_scratch);
+    if (d_norm_out) hipFree(d_norm_out);
     if (d_vals) hipFree(d_vals);
     if (d_gitems) hipFree(d_gitems);
     if (d_titems) hipFree(d_titems);
@@ -817,6 +841,14 @@ struct LatticeShifts {
   }
 };
 inline int my_round(double x) { return int(floor(fabs(x) + 0.5) * (x < 0 ? -1 : 1)); }
+// handles of field probes start here; everything below is a DFT object's index
+constexpr int PROBE_BASE = 1 << 30;
+inline int dft_bad_handle(const mnl_fields *F, int h) {
+  if (h >= PROBE_BASE)
+    return fail("handle " + std::to_string(h) + " is a field probe, not a DFT object: it has "
+                "no DFT data (read it with mnl_fields_probe_read)");
+  return h < 0 || h >= (int)F->dfts.size() ? fail("bad dft handle") : 0;
+}
 inline size_t dft_at(size_t p, size_t i, size_t nf) { return ((p >> 6) * nf + i) * 64 + (p & 63); }
 void dft_boundary_weights(const mnl_structure &S, const double wmin[3], const double wmax[3],
                           const int is[3], const int ie[3], double s0[3], double e0[3],
@@ -827,6 +859,7 @@ int dft_add_flux(mnl_fields *F, int nreg, const double *regions, const double *f
                  int decim);
 int dft_add_fields(mnl_fields *F, int ncomp, const int *comps, const double wmin[3],
                    const double wmax[3], const double *freqs, int nfreq, int yee, int decimation);
+int dft_block();
 int dft_prepare(mnl_fields *F, long long t0, int ns);
 int dft_flush(mnl_fields *F, DftFluxH &o);
 long long dft_plan_key(const mnl_fields *F);
@@ -850,6 +883,19 @@ const char *dft_list_name(const DftFluxH &o, int which);
 int dft_get(mnl_fields *F, int h, int which, double *out, long long n);
 int dft_load(mnl_fields *F, int h, int which, const double *in, long long n, int sign);
 int dft_scale(mnl_fields *F, int h, double re, double im);
+// ---- mnl_probe.cpp: field probes, dft_norm
+void dft_sampled_rebuild(mnl_fields *F);
+int probe_flush(mnl_fields *F, DftFluxH &o);
+int probe_add(mnl_fields *F, int c, const double pos[3]);
+int probe_read(mnl_fields *F, int h, long long cap, long long *count, long long *t_first,
+               double *values);
+int probe_reset(mnl_fields *F, int h);
+void probe_restart(mnl_fields *F);
+int probe_remove(mnl_fields *F, int h);
+int probe_remove_all(mnl_fields *F);
+int dft_norm(mnl_fields *F, double *out);
+double dft_maxfreq(const mnl_fields *F);
+int dft_max_decimation(const mnl_fields *F);
 int dft_save(mnl_fields *F, int h, const char *path);
 int dft_load_file(mnl_fields *F, int h, const char *path, int sign);
 int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,

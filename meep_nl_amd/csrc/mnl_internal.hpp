@@ -506,6 +506,12 @@ constexpr int PS_MAX_WG = 1024;    // workgroups along x per sum at most
 constexpr int PS_WG_PTS = 4096;    // pair points per workgroup at least (a multiple of 256)
 // PairRun: mnl_pair_runs.hpp
 
+// fields::dft_norm: the sum of |dft|^2 over an object's array, split into
+// workgroups of whole 64-slot blocks by the object's size alone
+constexpr int NORM_WAVES = 4;          // waves per workgroup (a wave takes whole blocks)
+constexpr int NORM_MAX_WG = 1024;      // workgroups per object at most
+constexpr int NORM_WG_BLOCKS = 16;     // 64-slot blocks per workgroup at least
+
 // =============================================================== launchers
 // Host-side launchers of the kernels, one heading per kernel file.  Each but k_cu_count
 // returns 0, or a non-zero code when an argument is bad or the launch failed.
@@ -604,6 +610,14 @@ int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream);
 int k_n2f_reduce(const double *part, double *out, int nwg, long long n, void *stream);
 int k_dft_pair_sum(const double *dft, const PairRun *runs, int nruns, long long total, int wg_pts,
                    int nwg, int nfreq, long long npad, double *part, void *stream);
+// part[wg] = the sum of |dft|^2 over the workgroup's blocks of this rank's slots (pj >= 0);
+// k_n2f_reduce adds the partial sums in workgroup order
+int k_dft_norm(const double *dft, const int *pj, long long npts, int nfreq, long long nblk,
+               long long wg_blocks, int nwg, double *part, void *stream);
+// field probe: row u of the n buffered rows fr[u][npts] -> series[(start + u) % cap], the row's
+// points added in list order (pslot[i]: slot of list point i, -1 another rank's)
+int k_probe_append(const double *fr, long long npts, int n, const int *pslot, int nlist,
+                   double *series, int cap, int start, void *stream);
 
 // ---- mnl_kernels_io.hip: what mnl_io.cpp and the ABI's getters launch
 int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,

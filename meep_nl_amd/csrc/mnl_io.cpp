@@ -160,6 +160,7 @@ int fields_load(mnl_fields *F, const char *path) {
   }
   if (matched != nfield) return fail("fields file does not match these fields (allocated arrays differ)");
   F->t = h.t;
+  probe_restart(F);  // probes are not part of a dump: empty at the loaded step
   // the loaded state comes from fields that were stepped: H and the W fields are
   // already separate (a dump taken before the first step holds zeros in them)
   F->e_first_done = F->h_first_done = true;
@@ -184,7 +185,7 @@ static int dft_file_lists(const DftFluxH &o) {
 }
 
 int dft_save(mnl_fields *F, int h, const char *path) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   DftFluxH &o = *F->dfts[h];
   const int nlists = dft_file_lists(o);
   std::vector<std::vector<double>> data(nlists);
@@ -231,7 +232,7 @@ int dft_save(mnl_fields *F, int h, const char *path) {
 }
 
 int dft_load_file(mnl_fields *F, int h, const char *path, int sign) {
-  if (h < 0 || h >= (int)F->dfts.size()) return fail("bad dft handle");
+  if (dft_bad_handle(F, h)) return -1;
   if (sign != 1 && sign != -1) return fail("dft_load_file: sign must be 1 or -1");
   DftFluxH &o = *F->dfts[h];
   FILE *fp = fopen(path, "rb");

@@ -727,6 +727,79 @@ int k_dft_pair_sum(const double *dft, const PairRun *runs, int nruns, long long 
   return rc();
 }
 
+// ------------------------------------------------- norm of the DFT arrays
+// fields::dft_norm (src/dft.cpp:312-361): the sum of |dft|^2 over every frequency of this
+// rank's slots.  A wave takes whole 64-slot blocks of the workgroup's fixed range (lanes are
+// slots: a frequency is one contiguous 1-KB span), then one wave reduction and one LDS pass over
+// the waves in order.  No atomics: part[wg] is added in workgroup order by n2f_reduce_kernel and
+// the split depends on the object alone, so the value is the same bits in every call.
+__global__ void __launch_bounds__(64 * NORM_WAVES)
+    dft_norm_kernel(const double2 *__restrict__ dft, const int *__restrict__ pj, long long npts,
+                    int nfreq, long long nblk, long long wg_blocks, double *__restrict__ part) {
+  __shared__ double red[NORM_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long b0 = (long long)blockIdx.x * wg_blocks, b1 = min(b0 + wg_blocks, nblk);
+  double acc = 0.0;
+  for (long long b = b0 + wave; b < b1; b += NORM_WAVES) {
+    const long long s = b * 64 + lane;
+    if (s >= npts || pj[3 * s] < 0) continue;  // the padded tail, another rank's slot
+    const double2 *__restrict__ dp = dft + b * nfreq * 64 + lane;
+    for (int i = 0; i < nfreq; i++) {
+      const double2 v = dp[(long long)i * 64];
+      acc += v.x * v.x + v.y * v.y;
+    }
+  }
+  const double v = n2f_wave_sum(acc);
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = red[0];
+#pragma unroll
+    for (int k = 1; k < NORM_WAVES; k++) t += red[k];
+    part[blockIdx.x] = t;
+  }
+}
+
+int k_dft_norm(const double *dft, const int *pj, long long npts, int nfreq, long long nblk,
+               long long wg_blocks, int nwg, double *part, void *stream) {
+  if (npts <= 0 || nfreq < 1 || nwg <= 0) return 0;
+  if (wg_blocks < 1 || nblk != (npts + 63) / 64) return 2;
+  if ((long long)nwg * wg_blocks < nblk) return 2;  // every block belongs to a workgroup
+  dft_norm_kernel<<<(unsigned)nwg, 64 * NORM_WAVES, 0, (hipStream_t)stream>>>(
+      (const double2 *)dft, pj, npts, nfreq, nblk, wg_blocks, part);
+  return rc();
+}
+
+// ------------------------------------------------- field probe
+// The flush of a probe (fields::get_field recorded every step): the
+// samplers have put w[i] * v[i] of update u into fr[u][slot]; one thread per buffered update
+// forms res = 0; res += w[i] * v[i] over the list's points in list order, skipping the points
+// another rank owns, and stores it in the ring.  When more rows are buffered than the ring
+// holds, only the newest `cap` rows are stored (each index written once).
+__global__ void __launch_bounds__(64)
+    probe_append_kernel(const double *__restrict__ fr, long long npts, int n,
+                        const int *__restrict__ pslot, int nlist, double *__restrict__ series,
+                        int cap, int start) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n || u < n - cap) return;
+  double res = 0.0;
+  for (int i = 0; i < nlist; i++) {
+    const int s = pslot[i];
+    if (s >= 0) res += fr[(long long)u * npts + s];
+  }
+  series[(int)(((long long)start + u) % cap)] = res;
+}
+
+int k_probe_append(const double *fr, long long npts, int n, const int *pslot, int nlist,
+                   double *series, int cap, int start, void *stream) {
+  if (n <= 0) return 0;
+  if (n > DFT_KB || nlist < 1 || nlist > 8 || npts < nlist || cap < 1 || start < 0 || start >= cap)
+    return 2;
+  probe_append_kernel<<<(unsigned)((n + 63) / 64), 64, 0, (hipStream_t)stream>>>(
+      fr, npts, n, pslot, nlist, series, cap, start);
+  return rc();
+}
+
 int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream) {
   if (a.npts <= 0 || nwg <= 0) return 0;
   if (a.nfreq < 1 || a.nruns < 1 || a.wg_blocks < 1) return 2;

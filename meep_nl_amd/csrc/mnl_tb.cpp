@@ -98,10 +98,10 @@ static int tb_plan(mnl_fields *F) {
   // the two-step items store step n+1 there too (the middle-step sample reads the mid set)
   std::vector<Box> dbox;
   std::vector<DftFluxH *> cmon;  // monitors whose box the two-step kernel stores compactly
-  for (auto &op : F->dfts) {  // (built once per monitor: this runs every batch)
+  for (DftFluxH *op : F->sampled) {  // (built once per monitor: this runs every batch)
     if (op->bbox.hi[0] < 0) continue;
     if (F->dft_cmp && op->cmp_cells && (int)cmon.size() < TB_MAXCMP)
-      cmon.push_back(op.get());
+      cmon.push_back(op);
     else
       dbox.push_back(op->bbox);
   }
@@ -131,7 +131,7 @@ static int tb_plan(mnl_fields *F) {
   F->tb_ritems.clear(), F->tb_rgeo.clear(), F->tb_items.clear();
   // compact DFT boxes: allocated once, emptied (DFT_CMP_EMPTY) with every new plan
   F->tb_cmp.clear();
-  for (auto &op : F->dfts) op->cmp_on = false;
+  for (DftFluxH *op : F->sampled) op->cmp_on = false;
   for (auto *o : cmon) {
     const size_t nd = (size_t)12 * o->cmp_cells;
     if (!o->d_cmp && hipMalloc(&o->d_cmp, nd * 8) != hipSuccess) {

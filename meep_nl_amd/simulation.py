@@ -819,25 +819,218 @@ def combine_step_funcs(*step_funcs):
     return _combine
 
 
-def stop_when_fields_decayed(dt=None, c=None, pt=None, decay_by=None):
-    """python/simulation.py:5225-5273: every dt time units compare the maximum
-    |c(pt)|^2 of the last interval with the maximum so far."""
-    if dt is None or c is None or pt is None or decay_by is None:
-        raise ValueError("dt, c, pt, and decay_by are all required.")
-    closure = {"max_abs": 0, "cur_max": 0, "t0": 0}
+# Conditions that speak the batched protocol.  Called as cond(sim) they
+# are the reference's closures, one evaluation per state.  _run_until may instead step many
+# steps per call when every condition offers
+#   batch_begin(sim) / batch_end(sim)  -- around the batched run (a probe is added / removed)
+#   batch_steps(sim, t, dt)  -- how many steps from step t until the first state at which the
+#       condition does more than look at the clock (>= 1, None: never)
+#   batch_fetch(sim, t, n)   -- take in what happened during the n steps after step t
+#   at_step(sim, t, rt)      -- cond(sim) for the state after step t, whose round_time() is rt:
+#       the same statements in the same order on the recorded values; the simulation itself
+#       is only looked at when the state is the current one (the end of a batch)
+def _round_time_at(t, dt):
+    return float(np.float32(t * dt))  # core.Fields.round_time
 
-    def _stop(sim):
-        v = sim.get_field_point(c, pt)
+
+_BATCH_MAX = 1 << 14  # steps per call at most (a probe's series holds 2^16)
+
+
+def _steps_until(t, dt, pred, limit=_BATCH_MAX):
+    """The least n in 1..limit with pred(round_time of step t + n), or limit; pred is monotone
+    (false, then true) in the time."""
+    hi = 1
+    while hi < limit and not pred(_round_time_at(t + hi, dt)):
+        hi *= 2
+    lo, hi = hi // 2, min(hi, limit)  # pred is false at lo (or lo is 0)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if pred(_round_time_at(t + mid, dt)):
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+class _Condition:
+    def __call__(self, sim):
+        return self.at_step(sim, None, sim.round_time())
+
+    def batch_begin(self, sim):
+        pass
+
+    def batch_end(self, sim):
+        pass
+
+    def batch_fetch(self, sim, t, n):
+        pass
+
+
+class _FieldsDecayed(_Condition):
+    def __init__(self, dt, c, pt, decay_by):
+        self.dt, self.c, self.pt, self.decay_by = dt, c, pt, decay_by
+        self.closure = {"max_abs": 0, "cur_max": 0, "t0": 0}
+        self._probe = None
+        self._values = {}
+
+    def at_step(self, sim, t, rt):
+        closure, dt = self.closure, self.dt
+        v = sim.get_field_point(self.c, self.pt) if t is None else self._values.pop(t)
         fabs = abs(v) * abs(v)
         closure["cur_max"] = max(closure["cur_max"], fabs)
-        if sim.round_time() <= dt + closure["t0"]:
+        if rt <= dt + closure["t0"]:
             return False
         old_cur = closure["cur_max"]
         closure["cur_max"] = 0
-        closure["t0"] = sim.round_time()
+        closure["t0"] = rt
         closure["max_abs"] = max(closure["max_abs"], old_cur)
-        return old_cur <= closure["max_abs"] * decay_by
-    return _stop
+        return old_cur <= closure["max_abs"] * self.decay_by
+
+    def batch_begin(self, sim):
+        self._values = {}
+        self._probe = sim.fields.add_probe(self.c, tuple(self.pt))
+
+    def batch_end(self, sim):
+        if self._probe is not None:
+            sim.fields.remove_probe(self._probe)
+        self._probe = None
+
+    def batch_steps(self, sim, t, dt):
+        lim = self.dt + self.closure["t0"]
+        return _steps_until(t, dt, lambda rt: rt > lim)
+
+    def batch_fetch(self, sim, t, n):
+        t_first, values = sim.fields.probe_read(self._probe)
+        if t_first != t + 1 or len(values) != n:
+            raise RuntimeError("stop_when_fields_decayed: the probe delivered steps %d..%d, "
+                               "expected %d..%d (series overrun: MNL_PROBE_CAP too small?)"
+                               % (t_first, t_first + len(values) - 1, t + 1, t + n))
+        for k in range(n):
+            self._values[t + 1 + k] = float(values[k])
+
+
+def stop_when_fields_decayed(dt=None, c=None, pt=None, decay_by=None):
+    """python/simulation.py:5225-5273: every dt time units compare the maximum
+    |c(pt)|^2 of the last interval with the maximum so far.  In a batched run the values come
+    from a device probe (core.Fields.add_probe) instead of one get_field call per step."""
+    if dt is None or c is None or pt is None or decay_by is None:
+        raise ValueError("dt, c, pt, and decay_by are all required.")
+    return _FieldsDecayed(dt, c, pt, decay_by)
+
+
+class _EnergyDecayed(_Condition):
+    def __init__(self, dt, decay_by):
+        self.dt, self.decay_by = dt, decay_by
+        self.closure = {"max_abs": 0, "t0": 0}
+
+    def at_step(self, sim, t, rt):
+        closure, dt = self.closure, self.dt
+        if rt <= dt + closure["t0"]:
+            return False
+        # (upstream: center=sim.geometry_center; this Simulation has none, its cell is centred
+        # on the origin.  The prints are the master's alone, as every print of this module.)
+        cell_volume = Volume(center=Vector3(), size=sim.cell_size)
+        cur_abs = abs(sim.field_energy_in_box(box=cell_volume))
+        closure["max_abs"] = max(closure["max_abs"], cur_abs)
+        closure["t0"] = rt
+        if closure["max_abs"] != 0 and verbosity.meep > 0 and sim._is_master():
+            print("energy decay(t = {}): {} / {} = {}".format(
+                sim.meep_time(), cur_abs, closure["max_abs"], cur_abs / closure["max_abs"]))
+        return cur_abs <= closure["max_abs"] * self.decay_by
+
+    def batch_steps(self, sim, t, dt):
+        lim = self.dt + self.closure["t0"]
+        return _steps_until(t, dt, lambda rt: rt > lim)
+
+
+def stop_when_energy_decayed(dt=None, decay_by=None):
+    """python/simulation.py:5276-5317: every dt time units compare the field energy of the
+    whole cell with its maximum so far."""
+    if dt is None or decay_by is None:
+        raise ValueError("dt and decay_by are all required.")
+    return _EnergyDecayed(dt, decay_by)
+
+
+class _DftDecayed(_Condition):
+    def __init__(self, tol, minimum_run_time, maximum_run_time):
+        self.tol, self.tmin, self.tmax = tol, minimum_run_time, maximum_run_time
+        self.closure = {"previous_fields": 0, "t0": 0, "dt": 0, "maxchange": 0}
+
+    def at_step(self, sim, t, rt):
+        closure = self.closure
+        if t is None:
+            t = sim.fields.t
+        if t == 0:  # (as upstream: the interval is set only by a call at the very first state)
+            closure["dt"] = max(1 / sim.fields.dft_maxfreq() / sim.fields.dt,
+                                sim.fields.max_decimation())
+        if self.tmax and rt > self.tmax:
+            return True
+        elif t <= closure["dt"] + closure["t0"]:
+            return False
+        previous_fields = closure["previous_fields"]
+        current_fields = sim.fields.dft_norm()
+        change = np.abs(previous_fields - current_fields)
+        closure["maxchange"] = max(closure["maxchange"], change)
+        if previous_fields == 0:
+            closure["previous_fields"] = current_fields
+            return False
+        closure["previous_fields"] = current_fields
+        closure["t0"] = t
+        if verbosity.meep > 1 and sim._is_master():
+            print("DFT fields decay(t = {0:0.2f}): {1:0.4e}".format(
+                sim.meep_time(), np.real(change / closure["maxchange"])))
+        return (change / closure["maxchange"]) <= self.tol and rt >= self.tmin
+
+    def batch_steps(self, sim, t, dt):
+        n = max(1, int(math.floor(self.closure["dt"] + self.closure["t0"])) + 1 - t)
+        if self.tmax:
+            n = min(n, _steps_until(t, dt, lambda rt: rt > self.tmax, n))
+        return n
+
+
+def stop_when_dft_decayed(tol=1e-11, minimum_run_time=0, maximum_run_time=None):
+    """python/simulation.py:5357-5402: every 1 / (largest DFT frequency) (or largest
+    decimation factor) steps compare the change of fields::dft_norm() with its largest change
+    so far."""
+    return _DftDecayed(tol, minimum_run_time, maximum_run_time)
+
+
+class _AfterTime(_Condition):
+    """until = a number T: round_time() >= t0 + T"""
+
+    def __init__(self, stop):
+        self.stop = stop
+
+    def at_step(self, sim, t, rt):
+        return rt >= self.stop
+
+    def batch_steps(self, sim, t, dt):
+        return _steps_until(t, dt, lambda rt: rt >= self.stop)
+
+
+class _AndAfterSources(_Condition):
+    """_run_sources_until's cond(sim) and round_time() >= ts, keeping cond's protocol"""
+
+    def __init__(self, cond, ts):
+        self.cond, self.ts = cond, ts
+
+    def __call__(self, sim):
+        return self.cond(sim) and sim.round_time() >= self.ts
+
+    def at_step(self, sim, t, rt):
+        return self.cond.at_step(sim, t, rt) and rt >= self.ts
+
+    def batch_begin(self, sim):
+        self.cond.batch_begin(sim)
+
+    def batch_end(self, sim):
+        self.cond.batch_end(sim)
+
+    def batch_steps(self, sim, t, dt):
+        return self.cond.batch_steps(sim, t, dt)
+
+    def batch_fetch(self, sim, t, n):
+        self.cond.batch_fetch(sim, t, n)
 
 
 def stop_after_walltime(t):
@@ -1292,6 +1485,9 @@ class Simulation:
                     batch *= 2
             self._run_finished()
             return
+        if not step_funcs and all(isinstance(c, (numbers.Number, _Condition)) for c in conds):
+            self._run_until_batched(conds, t0)
+            return
         for i, c in enumerate(conds):
             if isinstance(c, numbers.Number):
                 step_funcs.append(_progress(t0, c, self.progress_interval))
@@ -1306,6 +1502,44 @@ class Simulation:
             _eval_step_func(self, fn, "step")
         for fn in step_funcs:
             _eval_step_func(self, fn, "finish")
+        self._run_finished()
+
+    def _run_until_batched(self, conds, t0):
+        """The loop of _run_until for conditions that are numbers or speak the batched protocol
+        (no step functions): the same states go through the same conditions in the same order,
+        but fields.step is called once per stretch in which every condition only watches the
+        clock, and what the conditions would have read meanwhile is replayed from what the
+        device recorded."""
+        shows = [_progress(t0, c, self.progress_interval) for c in conds
+                 if isinstance(c, numbers.Number)]
+        conds = [_AfterTime(t0 + c) if isinstance(c, numbers.Number) else c for c in conds]
+        # the state the run starts from: evaluated as the one-step loop does
+        if not any(c(self) for c in conds):
+            t, dt = self.fields.t, self.fields.dt
+            begun = []
+            try:
+                for c in conds:
+                    c.batch_begin(self)
+                    begun.append(c)
+                done = False
+                while not done:
+                    n = min(_BATCH_MAX, min(c.batch_steps(self, t, dt) for c in conds))
+                    self.fields.step(n)
+                    for c in conds:
+                        c.batch_fetch(self, t, n)
+                    for k in range(1, n + 1):
+                        rt = _round_time_at(t + k, dt)
+                        if any(c.at_step(self, t + k, rt) for c in conds):
+                            if k != n:
+                                raise RuntimeError("batched run: a condition held %d steps "
+                                                   "before the end of its batch" % (n - k))
+                            done = True
+                    t += n
+                    for show in shows:
+                        show(self)
+            finally:
+                for c in begun:
+                    c.batch_end(self)
         self._run_finished()
 
     def _is_master(self):
@@ -1389,7 +1623,8 @@ class Simulation:
             if isinstance(c, numbers.Number):
                 new.append((ts - self.round_time()) + c)
             else:
-                new.append((lambda f: lambda sim: f(sim) and sim.round_time() >= ts)(c))
+                new.append(_AndAfterSources(c, ts) if isinstance(c, _Condition) else
+                           (lambda f: lambda sim: f(sim) and sim.round_time() >= ts)(c))
         self._run_until(new, step_funcs)
 
     # -- flux spectra
