@@ -343,14 +343,44 @@ int mnl_fields_traffic_model(mnl_fields *f, double *bytes_per_cell_step, double 
  * to the owned point one lattice vector away with phase 1 (connect_the_chunks,
  * src/boundaries.cpp:347-623), and the ghost planes are copied on the device after the E and
  * the H updates.  The fields stay real.  Accepted only before sources,
- * DFT monitors and the first step.  Fails with a "meep: ..." message for k != 0 (complex fields
- * are not supported), a PML on either side of the direction, a 1-D cell, a direction the cell
- * does not have, the slab direction of fields on more than one rank, and (PML along two
+ * DFT monitors and the first step.  Fails with a "meep: ..." message for k != 0 on real fields
+ * (it needs complex fields: mnl_fields_use_complex_fields first), a PML on either side of the
+ * direction, a 1-D cell, a direction the cell does not have, the slab direction of fields on more than one rank, and (PML along two
  * directions only) anisotropic susceptibilities or Newton-Raphson / off-diagonal chi1inv with a
  * susceptibility.  One rank steps periodic
  * 3-D runs in the fused mode like any other run (the top plane of each periodic direction as
  * shell boxes); pairs of steps, and the fused mode on several ranks, are declined. */
 int mnl_fields_use_bloch(mnl_fields *f, int dir, double k_re, double k_im);
+/* Complex fields: the inverse of fields::use_real_fields
+ * (src/fields.cpp:140-160).  Fields are real when created (a project default: meep::fields are
+ * complex until use_real_fields is called).  After this call the fields hold a second set of
+ * every time-stepped array (part 1, the imaginary part), stepped by the same kernels;
+ * mnl_fields_use_bloch then takes any complex k (in units of 2 pi, as fields::use_bloch,
+ * src/boundaries.cpp:88-103), and the ghost planes are multiplied by the Bloch phase on the
+ * device.  Sources add real(A J) to part 0 and imag(A J) to part 1 (src/step.cpp:300-315).
+ * Accepted only before use_bloch, sources, monitors, initialize_field and the first step, in
+ * 2-D and 3-D cells; on several ranks (every rank makes the call) the two parts' halo planes
+ * travel in one exchange group and the steps run unfused.  Fails with a "meep: ..." message for chi(2) / chi(3) media,
+ * off-diagonal chi1inv and anisotropic susceptibilities.  DFT flux and dft_fields objects
+ * accumulate phase * (f_re + i f_im) per update (src/dft.cpp:295-299), an image chunk's Bloch
+ * phase folded into its scale; near2far, energy and force objects, probes, dft_norm,
+ * checkpoints (dump / load), the tuner and pairs of steps are refused or inactive. */
+int mnl_fields_use_complex_fields(mnl_fields *f);
+/* fields::is_real (src/meep.hpp): *out = 1 for real fields, 0 after use_complex_fields */
+int mnl_fields_is_real(mnl_fields *f, int *out);
+/* fields::get_field(c, loc) (src/monitor.cpp:115-160) as a complex number (out[0] real, out[1]
+ * imaginary; 0 on real fields).  mnl_fields_get_field returns the real part. */
+int mnl_fields_get_field_complex(mnl_fields *f, int comp, const double pos[3], double out[2]);
+/* mnl_fields_copy_component / mnl_fields_array_slice of one part (0 real, 1 imaginary; part 1
+ * fails on real fields): fields_chunk::f[c][cmp] (src/meep.hpp) */
+int mnl_fields_copy_component_part(mnl_fields *f, int part, int comp, double *host, size_t n);
+int mnl_fields_array_slice_part(mnl_fields *f, int part, int comp, const double vmin[3],
+                                const double vmax[3], int snap, int *rank, long long dims[3],
+                                double *out, long long nout);
+/* fields::initialize_field with a complex function (src/initialize.cpp:135-160): re is added to
+ * part 0 and im (NULL: 0) to part 1.  Complex fields only. */
+int mnl_fields_initialize_field_complex(mnl_fields *f, int comp, const double *re,
+                                        const double *im, size_t n);
 /* boundary_condition of one side (0 low, 1 high) of a direction (src/meep.hpp: Periodic = 0,
  * Metallic = 1); fails for a direction the cell does not have. */
 enum { MNL_BOUNDARY_PERIODIC = 0, MNL_BOUNDARY_METALLIC = 1 };

@@ -96,6 +96,18 @@ _SIGS = {
     "mnl_fields_set_fused": (c_int, [c_void, c_int]),
     "mnl_fields_use_bloch": (c_int, [c_void, c_int, c_double, c_double]),
     "mnl_fields_boundary": (c_int, [c_void, c_int, c_int, iptr]),
+    # complex fields (the inverse of fields::use_real_fields, src/fields.cpp:140-160)
+    "mnl_fields_use_complex_fields": (c_int, [c_void]),
+    "mnl_fields_is_real": (c_int, [c_void, iptr]),
+    # fields::get_field without the real() (src/monitor.cpp:115-160)
+    "mnl_fields_get_field_complex": (c_int, [c_void, c_int, dptr, dptr]),
+    # fields_chunk::f[c][cmp] of one part
+    "mnl_fields_copy_component_part": (c_int, [c_void, c_int, c_int, dptr, c_size]),
+    "mnl_fields_array_slice_part": (c_int, [c_void, c_int, c_int, dptr, dptr, c_int, iptr,
+                                            ctypes.POINTER(ctypes.c_longlong), dptr,
+                                            ctypes.c_longlong]),
+    # fields::initialize_field with a complex function (src/initialize.cpp:135-160)
+    "mnl_fields_initialize_field_complex": (c_int, [c_void, c_int, dptr, dptr, c_size]),
     "mnl_fields_mode": (c_int, [c_void, iptr]),
     "mnl_fields_kernel_stats": (c_int, [c_void, c_int, llptr, dptr, dptr]),
     "mnl_fields_traffic_model": (c_int, [c_void, dptr, dptr]),

@@ -288,10 +288,24 @@ class Fields:
             self.h = None
 
     # -- boundaries
+    def use_complex_fields(self):
+        """The inverse of fields::use_real_fields (src/fields.cpp:140-160): a second set of
+        every time-stepped array (the imaginary part), after which use_bloch takes any complex
+        k.  Before use_bloch, sources, monitors, initialize_field and the first step."""
+        check(lib().mnl_fields_use_complex_fields(self.h))
+
+    @property
+    def is_real(self):
+        """fields::is_real: True until use_complex_fields()."""
+        v = ctypes.c_int(1)
+        check(lib().mnl_fields_is_real(self.h, ctypes.byref(v)))
+        return bool(v.value)
+
     def use_bloch(self, d, k=0):
-        """fields::use_bloch(d, k) (src/fields.cpp:75-90) for k = 0: both boundaries of
-        direction d (0 X, 1 Y, 2 Z) become periodic; the fields stay real.  Before sources,
-        DFT monitors and the first step."""
+        """fields::use_bloch(d, k) (src/boundaries.cpp:88-103): both boundaries of direction d
+        (0 X, 1 Y, 2 Z) become periodic with Bloch wavevector k (units of 2 pi; complex).  Real
+        fields take k = 0 only; after use_complex_fields() any k.  Before sources, DFT monitors
+        and the first step."""
         k = complex(k)
         check(lib().mnl_fields_use_bloch(self.h, int(d), k.real, k.imag))
 
@@ -414,6 +428,13 @@ class Fields:
         callable f(*coords) vectorised over the coordinate arrays of comp."""
         if callable(values):
             values = values(*self.gv.coords(comp))
+        if not self.is_real:  # imag(val) goes to part 1 (src/initialize.cpp:155-160)
+            z = np.broadcast_to(values, self.gv.shape())
+            re = np.ascontiguousarray(np.real(z), dtype=np.float64).ravel()
+            im = np.ascontiguousarray(np.imag(z), dtype=np.float64).ravel()
+            check(lib().mnl_fields_initialize_field_complex(self.h, comp, ptr(re), ptr(im),
+                                                            re.size))
+            return
         v = np.ascontiguousarray(np.real(np.broadcast_to(values, self.gv.shape())),
                                  dtype=np.float64).ravel()
         check(lib().mnl_fields_initialize_field(self.h, comp, ptr(v), v.size))
@@ -514,26 +535,48 @@ class Fields:
         check(lib().mnl_fields_get_field(self.h, comp, ptr(pos), ctypes.byref(out)))
         return out.value
 
-    def get_array(self, comp):
+    def get_field_complex(self, comp, pos):
+        """fields::get_field(c, loc) (src/monitor.cpp:115-160) as a complex number; get_field
+        returns its real part."""
+        pos = np.ascontiguousarray(list(pos) + [0.0] * (3 - len(pos)), dtype=np.float64)
+        out = np.zeros(2)
+        check(lib().mnl_fields_get_field_complex(self.h, comp, ptr(pos), ptr(out)))
+        return complex(out[0], out[1])
+
+    def get_array(self, comp, part=0, cmplx=False):
+        """The whole-cell array of comp: the real part (part 0), the imaginary part (part 1,
+        complex fields only), or with cmplx=True both as a complex array."""
+        if cmplx:
+            re = self.get_array(comp, 0)
+            return re + 1j * (0.0 if self.is_real else self.get_array(comp, 1))
         nt = lib().mnl_fields_ntot(self.h)
         out = np.zeros(nt, dtype=np.float64)
-        check(lib().mnl_fields_copy_component(self.h, comp, ptr(out), nt))
+        check(lib().mnl_fields_copy_component_part(self.h, int(part), comp, ptr(out), nt))
         return out.reshape(self.gv.shape())
 
-    def get_array_slice(self, comp, vmin, vmax, snap=False):
+    def get_array_slice(self, comp, vmin, vmax, snap=False, part=0, cmplx=False):
         """fields::get_array_slice(volume, c) (src/array_slice.cpp:611-704) over
         [vmin, vmax] (3 coordinates): Centered-grid values, empty dimensions
-        interpolated and collapsed; shape = kept directions in X, Y, Z order."""
+        interpolated and collapsed; shape = kept directions in X, Y, Z order.  part selects
+        the real (0) or the imaginary (1) part of complex fields; cmplx=True returns a complex
+        array."""
+        if cmplx:
+            re = self.get_array_slice(comp, vmin, vmax, snap, 0)
+            # (epsilon and mu are real: src/array_slice.cpp:385-408)
+            derived = comp in (Dielectric, Permeability)
+            im = 0.0 if self.is_real or derived else self.get_array_slice(comp, vmin, vmax, snap, 1)
+            return re + 1j * im
         lo = np.ascontiguousarray(vmin, dtype=np.float64)
         hi = np.ascontiguousarray(vmax, dtype=np.float64)
         rank = ctypes.c_int(0)
         dims = (ctypes.c_longlong * 3)()
-        check(lib().mnl_fields_array_slice(self.h, comp, ptr(lo), ptr(hi), int(snap),
-                                           ctypes.byref(rank), dims, None, 0))
+        check(lib().mnl_fields_array_slice_part(self.h, int(part), comp, ptr(lo), ptr(hi),
+                                                int(snap), ctypes.byref(rank), dims, None, 0))
         shape = tuple(dims[k] for k in range(rank.value))
         out = np.zeros(int(np.prod(shape)) if shape else 1)
-        check(lib().mnl_fields_array_slice(self.h, comp, ptr(lo), ptr(hi), int(snap),
-                                           ctypes.byref(rank), dims, ptr(out), out.size))
+        check(lib().mnl_fields_array_slice_part(self.h, int(part), comp, ptr(lo), ptr(hi),
+                                                int(snap), ctypes.byref(rank), dims, ptr(out),
+                                                out.size))
         return out.reshape(shape) if shape else out[0]
 
     def center(self):

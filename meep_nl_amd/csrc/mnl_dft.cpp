@@ -95,6 +95,12 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
   std::vector<DftChunkH> made;
   LatticeShifts ls(S, F->periodic, wmin, wmax);  // src/loop_in_chunks.cpp:390-532
   do {
+  // complex fields: the lattice shift's Bloch phase (src/loop_in_chunks.cpp:409-416), which
+  // dft_chunk folds into scale (src/dft.cpp:98, 171); real fields: 1
+  cplx shift_phase = 1.0;
+  if (is_complex(F))
+    for (int d = 0; d < 3; d++)
+      if (S.has[d]) shift_phase *= pow((F->part0 ? F->part0 : F)->eikna[d], ls.cur[d]);
   for (auto &ch : reference_chunks(S)) {
     int isc[3], iec[3];
     double s0c[3], s1c[3], e0c[3], e1c[3];
@@ -144,7 +150,7 @@ void dft_add(mnl_fields *F, DftFluxH &o, int c, const double wmin[3], const doub
     }
     DftChunkH dc;
     dc.c = c;
-    dc.scale = stored_weight * cplx(1.0) * dt_factor;
+    dc.scale = stored_weight * (is_complex(F) ? shift_phase : cplx(1.0)) * dt_factor;
     int nun = 0;
     for (int d = 0; d < 3; d++)
       if (!yee && S.has[d] && !S.shift(c, d)) nun++;
@@ -930,6 +936,24 @@ int dft_flush(mnl_fields *F, DftFluxH &o) {
   if (o.kind == DFT_PROBE) return probe_flush(F, o);
   const size_t nch = dft_nchunks(o);
   const long long rstride = (long long)(nch * o.nfreq);
+  // Complex fields: part 1's object only samples; its rows are
+  // accumulated with part 0's, dft += phase * (f_re + i f_im) per update in update order
+  // (dft_chunk::update_dft, src/dft.cpp:295-299), into part 0's array, which every reader reads.
+  if (F->part0) return 0;
+  if (mnl_fields *T = F->twin.get()) {
+    size_t h = 0;
+    while (h < F->dfts.size() && F->dfts[h].get() != &o) h++;
+    if (h >= T->dfts.size()) return fail("dft: the parts of the complex fields differ");
+    DftFluxH &o1 = *T->dfts[h];
+    if (o1.nbuf != o.nbuf || o1.npts != o.npts)
+      return fail("dft: the parts of the complex fields differ");
+    if (k_dft_accum_cplx(o.d_pj, o.d_pch, o.d_dft, o.d_fr, o1.d_fr, o.nbuf,
+                         o.d_ph + 2 * (size_t)(o.row - o.nbuf) * rstride, rstride, o.nfreq,
+                         (long long)o.npts, F->stream))
+      return fail("dft accumulate launch failed");
+    o.nbuf = o1.nbuf = 0;
+    return 0;
+  }
   if (k_dft_accum(o.d_pj, o.d_pch, o.d_dft, o.d_fr, o.nbuf,
                   o.d_ph + 2 * (size_t)(o.row - o.nbuf) * rstride, rstride, o.nfreq,
                   (long long)o.npts, F->stream))

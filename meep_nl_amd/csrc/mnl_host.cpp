@@ -15,8 +15,11 @@ namespace mnlh {
 thread_local std::string g_err;
 int g_verbosity = 1;
 
+// share: the communicator of part 0 of complex fields, which part 1 (the fields created here)
+// uses for its slab of the same rank: every collective of part 1 follows part 0's on the same
+// host thread, in the same order on every rank
 static mnl_fields *create_common(mnl_structure *s, int device, int rank, int nranks, const void *id,
-                          LocalHub *hub = nullptr) {
+                          LocalHub *hub = nullptr, std::shared_ptr<Comm> share = nullptr) {
   if (!s) {
     fail("null structure");
     return nullptr;
@@ -44,7 +47,9 @@ static mnl_fields *create_common(mnl_structure *s, int device, int rank, int nra
   memset(&F->f, 0, sizeof(F->f));
   F->rank = rank;
   F->nranks = nranks;
-  if (nranks > 1) {
+  if (nranks > 1 && share) {
+    F->comm = share;
+  } else if (nranks > 1) {
     F->comm.reset(new Comm());
     if (hub ? F->comm->init_local(rank, nranks, hub) : F->comm->init(rank, nranks, id)) {
       fail(hub ? "local slab group init failed"
@@ -122,6 +127,21 @@ static const SchedOpt SCHED_OPTS[] = {
     {MNL_SCHED_R1_BESIDE, "r1_beside", &mnl_fields::tb_r1a, nullptr, 0, 0, nullptr, true},
     {MNL_SCHED_SRC_GUARD, "src_guard", &mnl_fields::tb_srcguard, nullptr, 0, 0, nullptr, false},
 };
+
+// a source of complex fields goes to both parts with the same amplitude A: part 0 adds
+// real(A J), part 1 imag(A J) (build_source_lists, source_table)
+static int add_source_parts(mnl_fields *F, int comp, int kind, const double *p, int np,
+                            mnl_src_func func, void *fdata, const double vmin[3],
+                            const double vmax[3], double amp_re, double amp_im, int is_integrated,
+                            mnl_amp_func afunc, void *adata) {
+  if (add_source_any(F, comp, kind, p, np, func, fdata, vmin, vmax, amp_re, amp_im, is_integrated,
+                     afunc, adata))
+    return -1;
+  if (F && F->twin)
+    return add_source_any(F->twin.get(), comp, kind, p, np, func, fdata, vmin, vmax, amp_re, amp_im,
+                          is_integrated, afunc, adata);
+  return 0;
+}
 
 }  // namespace mnlh
 
@@ -378,7 +398,7 @@ int mnl_fields_add_point_source(mnl_fields *F, int comp, int kind, const double 
                                 const double pos[3], double amp_re, double amp_im,
                                 int is_integrated) {
   if (!pos) return fail("null position");
-  return add_source_any(F, comp, kind, p, np, nullptr, nullptr, pos, pos, amp_re, amp_im,
+  return add_source_parts(F, comp, kind, p, np, nullptr, nullptr, pos, pos, amp_re, amp_im,
                         is_integrated, nullptr, nullptr);
 }
 
@@ -388,7 +408,7 @@ int mnl_fields_add_volume_source(mnl_fields *F, int comp, int kind, const double
                                  void *adata) {
   if (!vmin || !vmax) return fail("null volume");
   if (kind == MNL_SRC_CUSTOM) return fail("custom sources: use mnl_fields_add_custom_volume_source");
-  return add_source_any(F, comp, kind, p, np, nullptr, nullptr, vmin, vmax, amp_re, amp_im,
+  return add_source_parts(F, comp, kind, p, np, nullptr, nullptr, vmin, vmax, amp_re, amp_im,
                         is_integrated, afunc, adata);
 }
 
@@ -399,7 +419,7 @@ int mnl_fields_add_custom_volume_source(mnl_fields *F, int comp, mnl_src_func fu
   if (!func) return fail("custom source needs a function");
   if (!vmin || !vmax) return fail("null volume");
   const double p[2] = {start_time, end_time};
-  return add_source_any(F, comp, MNL_SRC_CUSTOM, p, 2, func, data, vmin, vmax, amp_re, amp_im,
+  return add_source_parts(F, comp, MNL_SRC_CUSTOM, p, 2, func, data, vmin, vmax, amp_re, amp_im,
                         is_integrated, afunc, adata);
 }
 
@@ -409,7 +429,7 @@ int mnl_fields_add_custom_point_source(mnl_fields *F, int comp, mnl_src_func fun
   if (!func) return fail("custom source needs a function");
   const double p[2] = {start_time, end_time};
   if (!pos) return fail("null position");
-  return add_source_any(F, comp, MNL_SRC_CUSTOM, p, 2, func, data, pos, pos, amp_re, amp_im,
+  return add_source_parts(F, comp, MNL_SRC_CUSTOM, p, 2, func, data, pos, pos, amp_re, amp_im,
                         is_integrated, nullptr, nullptr);
 }
 
@@ -417,6 +437,7 @@ int mnl_fields_require_component(mnl_fields *F, int comp) {
   if (!F || check_comp(comp)) return -1;
   if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (F->twin && require_component(F->twin.get(), comp)) return -1;
   return require_component(F, comp);
 }
 
@@ -432,11 +453,13 @@ int mnl_fields_tune(mnl_fields *F, int reps, int *zchunk, int *gen_cus) {
   if (zchunk) *zchunk = -1;
   if (gen_cus) *gen_cus = -1;
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "tune")) return -1;
   return tune(F, reps, zchunk, gen_cus);
 }
 
 int mnl_fields_initialize_field(mnl_fields *F, int comp, const double *host, size_t n) {
   if (!F || check_comp(comp) || !host) return fail("bad argument");
+  if (F->twin) return mnl_fields_initialize_field_complex(F, comp, host, nullptr, n);
   if (n < F->S.ntot) return fail("initialize_field: array smaller than the cell");
   if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
@@ -454,12 +477,19 @@ int mnl_fields_energy_in_box(mnl_fields *F, int which, const double vmin[3], con
     lo[d] = S.has[d] ? (vmin ? vmin[d] : S.io[d] * (0.5 / S.a)) : 0.0;
     hi[d] = S.has[d] ? (vmax ? vmax[d] : (S.io[d] + 2 * S.n[d]) * (0.5 / S.a)) : 0.0;
   }
-  return energy_in_box(F, which, lo, hi, out);
+  if (energy_in_box(F, which, lo, hi, out)) return -1;
+  if (F->twin) {  // real(conj(E) D) = E0 D0 + E1 D1 (src/energy_and_flux.cpp:54-187): both parts
+    double im = 0.0;
+    if (energy_in_box(F->twin.get(), which, lo, hi, &im)) return -1;
+    *out += im;
+  }
+  return 0;
 }
 
 int mnl_fields_set_nan_check(mnl_fields *F, int every) {
   if (!F || every < 1) return fail("NaN check cadence must be >= 1 step");
   F->nan_every = every;
+  if (F->twin) F->twin->nan_every = every;
   return 0;
 }
 
@@ -474,6 +504,7 @@ int mnl_fields_array_slice(mnl_fields *F, int comp, const double vmin[3], const 
 int mnl_fields_dump(mnl_fields *F, const char *filename) {
   if (!F || !filename) return fail("null argument");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "dump (checkpoints of complex fields are the follow-up)")) return -1;
   std::string p = filename;
   if (F->nranks > 1) p += ".rank" + std::to_string(F->rank);
   return fields_dump(F, p.c_str());
@@ -482,6 +513,7 @@ int mnl_fields_dump(mnl_fields *F, const char *filename) {
 int mnl_fields_load(mnl_fields *F, const char *filename) {
   if (!F || !filename) return fail("null argument");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "load (checkpoints of complex fields are the follow-up)")) return -1;
   std::string p = filename;
   if (F->nranks > 1) p += ".rank" + std::to_string(F->rank);
   return fields_load(F, p.c_str());
@@ -507,6 +539,7 @@ int mnl_fields_time(mnl_fields *F, long long *t, double *dt) {
 int mnl_fields_set_time(mnl_fields *F, long long t) {
   if (!F || t < 0) return fail("bad argument");
   F->t = t;
+  if (F->twin) F->twin->t = t;
   probe_restart(F);
   return 0;
 }
@@ -518,6 +551,7 @@ int mnl_fields_zero_fields(mnl_fields *F) {
   // rebuilt from the zeroed arrays when it is entered again).
   if (!F) return fail("null fields");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (F->twin && mnl_fields_zero_fields(F->twin.get())) return -1;
   if (F->fused && set_fused(F, false)) return -1;
   for (const CkEntry &e : ckpt_entries(F))
     if (e.kind != 11) HIPCHK(hipMemsetAsync(e.p, 0, e.n * sizeof(double), F->stream));
@@ -531,6 +565,7 @@ int mnl_fields_remove_sources(mnl_fields *F) {
   F->groups.clear();
   F->srcs.clear();
   F->src_dirty = true;
+  if (F->twin) return mnl_fields_remove_sources(F->twin.get());
   return 0;
 }
 
@@ -620,13 +655,114 @@ int mnl_fields_nr_fallbacks(mnl_fields *F, long long *count) {
   return 0;
 }
 
+int mnl_fields_use_complex_fields(mnl_fields *F) {
+  // the inverse of fields::use_real_fields (src/fields.cpp:140-160): a second set of every
+  // time-stepped array -- here a second fields object of the same structure (mnl_fields::twin)
+  if (!F) return fail("null fields");
+  if (F->twin) return 0;
+  if (F->part0) return fail("use_complex_fields: bad fields object");
+  if (F->S.dim == 1) return fail("use_complex_fields: 1-D cells are not supported");
+  bool chi = false, offd = false, aniso = false;
+  for (int c = 0; c < 3; c++) {
+    chi = chi || !all_eq(F->S.chi2[c], 0.0) || !all_eq(F->S.chi3[c], 0.0);
+    for (int d = 0; d < 3; d++) offd = offd || (d != c && !all_eq(F->S.chi1inv[c][d], 0.0));
+  }
+  for (const BoxSpec &b : F->S.boxes) chi = chi || (b.kind == 1 && b.value != 0.0);
+  for (const Lorentz &L : F->S.lor) aniso = aniso || L.aniso();
+  if (chi || F->nr || F->upnl)
+    return fail("use_complex_fields: chi(2) / chi(3) media are not supported on complex fields "
+                "(the Newton-Raphson solve on two parts is not built)");
+  if (offd || aniso || F->f.aniso)
+    return fail("use_complex_fields: off-diagonal chi1inv and anisotropic susceptibilities are "
+                "not supported on complex fields");
+  if (F->t != 0 || F->e_first_done || F->h_first_done || F->u_first_done[0] || F->u_first_done[1])
+    return fail("use_complex_fields: only before the first step");
+  if (!F->groups.empty() || !F->sampled.empty())
+    return fail("use_complex_fields: only before sources and DFT monitors are added");
+  if (any_periodic(F)) return fail("use_complex_fields: only before use_bloch");
+  for (int c = 0; c < MNL_NUM_COMPONENTS; c++)
+    if (F->allocated[c])
+      return fail("use_complex_fields: only before initialize_field and before any component is "
+                  "required");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (F->fused && set_fused(F, false)) return -1;
+  // several ranks (every rank makes this call): part 1 takes the same slab and shares part 0's
+  // communicator, so exchange lists both sets in one group
+  std::unique_ptr<mnl_fields> T(
+      create_common(&F->S, F->device, F->rank, F->nranks, nullptr, nullptr, F->comm));
+  if (!T) return -1;
+  // part 1 runs on part 0's stream: one sub-step of both parts is then in order before the
+  // wrap that follows it
+  HIPCHK(hipStreamSynchronize(T->stream));
+  HIPCHK(hipStreamDestroy(T->stream));
+  T->stream = F->stream;
+  T->part0 = F;
+  T->allow_fused = F->allow_fused;
+  T->nan_every = F->nan_every;
+  T->tb_enabled = false;
+  F->twin = std::move(T);
+  return 0;
+}
+
+int mnl_fields_is_real(mnl_fields *F, int *out) {
+  if (!F || !out) return fail("null argument");
+  *out = is_complex(F) ? 0 : 1;
+  return 0;
+}
+
+int mnl_fields_get_field_complex(mnl_fields *F, int comp, const double pos[3], double out[2]) {
+  // fields::get_field (src/monitor.cpp:115-160) without the real()
+  if (!F || !pos || !out || check_comp(comp)) return -1;
+  if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  out[1] = 0.0;
+  if (get_field(F, comp, pos, &out[0], true)) return -1;
+  return F->twin ? get_field(F->twin.get(), comp, pos, &out[1], true) : 0;
+}
+
+int mnl_fields_copy_component_part(mnl_fields *F, int part, int comp, double *host, size_t n) {
+  if (!F || part < 0 || part > 1) return fail("bad argument");
+  if (part == 1 && !F->twin) return fail("copy_component: real fields have no imaginary part");
+  return mnl_fields_copy_component(part ? F->twin.get() : F, comp, host, n);
+}
+
+int mnl_fields_array_slice_part(mnl_fields *F, int part, int comp, const double vmin[3],
+                                const double vmax[3], int snap, int *rank, long long dims[3],
+                                double *out, long long nout) {
+  if (!F || part < 0 || part > 1) return fail("bad argument");
+  if (part == 1 && !F->twin) return fail("array_slice: real fields have no imaginary part");
+  return mnl_fields_array_slice(part ? F->twin.get() : F, comp, vmin, vmax, snap, rank, dims, out,
+                                nout);
+}
+
+int mnl_fields_initialize_field_complex(mnl_fields *F, int comp, const double *re,
+                                        const double *im, size_t n) {
+  // fields::initialize_field adds real(val) to part 0 and imag(val) to part 1
+  // (src/initialize.cpp:155-160); im == NULL: 0.  Both parts take every step of the call (the
+  // lazy copies, update_eh, the ghost planes), so that they stay in the same state.
+  if (!F || check_comp(comp) || !re) return fail("bad argument");
+  if (!F->twin) return fail("initialize_field_complex: the fields are real");
+  if (n < F->S.ntot) return fail("initialize_field: array smaller than the cell");
+  if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  mnl_fields *T = F->twin.get();
+  if (require_component(F, comp) || require_component(T, comp)) return -1;
+  for (mnl_fields *p : {F, T})
+    if (p->fused && set_fused(p, false)) return -1;
+  std::vector<double> zero;
+  if (!im) zero.assign(F->S.ntot, 0.0), im = zero.data();
+  F->f.nr_t = T->f.nr_t = F->t;
+  if (initialize_field(F, comp, re) || initialize_field(T, comp, im)) return -1;
+  return 0;
+}
+
 int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
-  // fields::use_bloch (src/fields.cpp:75-90) with k = 0
+  // fields::use_bloch (src/boundaries.cpp:88-103); real fields: k = 0 only
   if (!F) return fail("null fields");
   if (dir < 0 || dir > 2) return fail("use_bloch: direction must be 0 (X), 1 (Y) or 2 (Z)");
-  if (k_re != 0.0 || k_im != 0.0)
-    return fail("use_bloch: k != 0 needs complex fields, which are not supported (only k = 0, "
-                "real fields)");
+  if ((k_re != 0.0 || k_im != 0.0) && !F->twin)
+    return fail("use_bloch: k != 0 needs complex fields (mnl_fields_use_complex_fields before "
+                "use_bloch); real fields take only k = 0");
   if (F->S.dim == 1) return fail("use_bloch: periodic boundaries of 1-D cells are not supported");
   if (!F->S.has[dir]) return fail("use_bloch: the cell has no such direction");
   if (F->S.pml_thick[dir][0] > 0 || F->S.pml_thick[dir][1] > 0)
@@ -634,7 +770,7 @@ int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
   if (F->nranks > 1 && dir == F->slab_dir)
     return fail("use_bloch: the slab direction of fields on more than one rank cannot be "
                 "periodic");
-  if (F->periodic[dir]) return 0;
+  if (F->periodic[dir] && !F->twin) return 0;
   {
     // The E / P kernels that read wall-plane neighbours of another reference chunk as 0
     // (on_wall: anisotropic sigma, and Newton-Raphson or upstream off-diagonal chi1inv with a
@@ -653,6 +789,12 @@ int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
     return fail("use_bloch: only before sources and DFT monitors are added");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   if (F->fused && set_fused(F, false)) return -1;
+  if (mnl_fields *T = F->twin.get()) {
+    if (T->fused && set_fused(T, false)) return -1;
+    F->eikna[dir] = bloch_eikna(cplx(k_re, k_im), F->S.n[dir], F->S.a);
+    if (F->periodic[dir]) return 0;  // k set again
+    if (set_periodic(T, dir)) return -1;
+  }
   return set_periodic(F, dir);
 }
 
@@ -667,13 +809,14 @@ int mnl_fields_set_fused(mnl_fields *F, int allow) {
   if (!F) return fail("null fields");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   F->allow_fused = allow != 0;
+  if (F->twin && mnl_fields_set_fused(F->twin.get(), allow)) return -1;
   if (!F->allow_fused) return set_fused(F, false);
   return 0;
 }
 
 int mnl_fields_set_profiling(mnl_fields *F, int on) {
   if (!F) return fail("null fields");
-  F->profiling = on != 0;
+  F->profiling = on != 0;  // (complex fields: part 0's timers time the launches of both parts)
   for (int k = 0; k < TM_CAP; k++) F->timer_ms[k] = 0, F->timer_count[k] = 0;
   return 0;
 }
@@ -686,12 +829,13 @@ int mnl_fields_kernel_stats(mnl_fields *F, int which, long long *launches, doubl
 
 int mnl_fields_set_temporal_blocking(mnl_fields *F, int on) {
   if (!F) return fail("null fields");
-  F->tb_enabled = on != 0;
+  F->tb_enabled = on != 0;  // (complex fields never step in pairs: part 1 keeps it off)
   return 0;
 }
 
 int mnl_fields_set_schedule(mnl_fields *F, int which, int value) {
   if (!F) return fail("null fields");
+  if (F->twin && mnl_fields_set_schedule(F->twin.get(), which, value)) return -1;  // both parts
   for (const SchedOpt &o : SCHED_OPTS) {
     if (o.id != which) continue;
     if (o.count && value != 0 && (value < o.lo || value > o.hi)) return fail(o.err);
@@ -730,6 +874,10 @@ int mnl_fields_add_dft_fields(mnl_fields *F, int ncomp, const int *comps, const 
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   const int h = dft_add_fields(F, ncomp, comps, vmin, vmax, freqs, nfreq, yee_grid, decimation);
   if (h < 0) return -1;
+  // complex fields: part 1 gets the same object (the same handle), which samples its rows
+  if (F->twin && dft_add_fields(F->twin.get(), ncomp, comps, vmin, vmax, freqs, nfreq, yee_grid,
+                                decimation) != h)
+    return fail("add_dft_fields: the parts of the complex fields differ");
   *handle = h;
   return 0;
 }
@@ -749,6 +897,8 @@ int mnl_fields_add_dft_flux(mnl_fields *F, int nreg, const double *regions, cons
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   const int h = dft_add_flux(F, nreg, regions, freqs, nfreq, decimation);
   if (h < 0) return -1;
+  if (F->twin && dft_add_flux(F->twin.get(), nreg, regions, freqs, nfreq, decimation) != h)
+    return fail("add_dft_flux: the parts of the complex fields differ");
   *handle = h;
   return 0;
 }
@@ -834,6 +984,7 @@ int mnl_fields_add_probe(mnl_fields *F, int comp, const double pos[3], int *hand
   if (check_comp(comp)) return -1;
   if (!has_field(F->S, comp)) return fail("component not present in this dimensionality");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "add_probe")) return -1;
   const int h = probe_add(F, comp, pos);
   if (h < 0) return -1;
   *handle = h;
@@ -868,6 +1019,7 @@ int mnl_fields_remove_probes(mnl_fields *F) {
 int mnl_fields_dft_norm(mnl_fields *F, double *norm) {
   if (!F || !norm) return fail("null argument");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "dft_norm")) return -1;
   return dft_norm(F, norm);
 }
 
@@ -898,6 +1050,7 @@ int mnl_fields_add_dft_near2far(mnl_fields *F, int nreg, const double *regions, 
     if (regions[8 * r + 6] < 0 || regions[8 * r + 6] > 2)
       return fail("invalid normal direction in dft_near2far!");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "add_dft_near2far")) return -1;
   const int h = dft_add_near2far(F, nreg, regions, freqs, nfreq, decimation, nperiods);
   if (h < 0) return -1;
   *handle = h;
@@ -930,6 +1083,7 @@ int mnl_fields_add_dft_energy(mnl_fields *F, int nreg, const double *regions, co
   if (!F || !regions || !freqs || !handle) return fail("null argument");
   if (decimation < 0) return fail("decimation must be >= 0");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "add_dft_energy")) return -1;
   const int h = dft_add_energy(F, nreg, regions, freqs, nfreq, decimation);
   if (h < 0) return -1;
   *handle = h;
@@ -941,6 +1095,7 @@ int mnl_fields_add_dft_force(mnl_fields *F, int nreg, const double *regions, con
   if (!F || !regions || !freqs || !handle) return fail("null argument");
   if (decimation < 0) return fail("decimation must be >= 0");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "add_dft_force")) return -1;
   const int h = dft_add_force(F, nreg, regions, freqs, nfreq, decimation);
   if (h < 0) return -1;
   *handle = h;

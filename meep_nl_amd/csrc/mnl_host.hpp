@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/meep_nl_amd.h"
+#include "mnl_bloch.hpp"
 #include "mnl_comm.hpp"
 #include "mnl_internal.hpp"
 
@@ -320,12 +321,21 @@ struct mnl_fields {
   int device = 0;
   hipStream_t stream = nullptr;
   int rank = 0, nranks = 1;
-  std::unique_ptr<Comm> comm;
+  std::shared_ptr<Comm> comm;  // (part 1 of complex fields shares part 0's)
   int slab_dir = 2;  // direction decomposed across ranks
   // fields::use_bloch with k = 0: both boundaries of the direction are
   // Periodic -- no metal wall, plane n of the unshifted components owned, the not-owned planes
   // copies of the owner one lattice vector away (wrap)
   bool periodic[3] = {false, false, false};
+  // complex fields (fields::use_real_fields undone).  Every step kernel is
+  // linear with real coefficients in the supported media, so the real and the imaginary part
+  // step as two real field sets: this object holds part 0 and owns `twin`, a second fields
+  // object of the same structure that holds part 1, shares this one's stream and is stepped in
+  // lockstep (step_batch_cplx).  The parts meet only at the ghost planes (wrap).  part0: the
+  // twin's way back.  eikna: fields::eikna (src/boundaries.cpp:88-99), 1 where not periodic.
+  std::unique_ptr<mnl_fields> twin;
+  mnl_fields *part0 = nullptr;
+  cplx eikna[3] = {1.0, 1.0, 1.0};
   DevGrid g;
   DevFields f;
   size_t nlocal = 0;  // doubles per local array
@@ -561,7 +571,7 @@ struct mnl_fields {
       if (e) hipEventDestroy(e);
     if (s_aux) hipStreamDestroy(s_aux);
     if (s_comm) hipStreamDestroy(s_comm);
-    if (stream) hipStreamDestroy(stream);
+    if (stream && !part0) hipStreamDestroy(stream);  // part 1 runs on part 0's stream
   }
 };
 
@@ -719,6 +729,12 @@ int dev_alloc(mnl_fields *F, T **p, size_t n, bool zero = true) {
 
 inline bool any_periodic(const mnl_fields *F) {
   return F->periodic[0] || F->periodic[1] || F->periodic[2];
+}
+inline bool is_complex(const mnl_fields *F) { return F->twin || F->part0; }
+// what complex fields do not do yet: `what` fails with the follow-up named
+inline int refuse_complex(const mnl_fields *F, const char *what) {
+  if (!is_complex(F)) return 0;
+  return fail(std::string(what) + " is not supported on complex fields yet");
 }
 inline int check_comp(int c) {
   if (c < 0 || c >= MNL_NUM_COMPONENTS) return fail("invalid component");

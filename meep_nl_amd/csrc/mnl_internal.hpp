@@ -590,6 +590,10 @@ int k_dft_sample(const int *pj, const double *pw, const int *pch, const DftChunk
                  long long npts, const DevGrid &g, const DevFields &f, void *stream);
 int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, int n,
                 const double *ph, long long rstride, int nfreq, long long npts, void *stream);
+// complex fields: dft += phase * (fr0 + i fr1) per buffered update (src/dft.cpp:295-299)
+int k_dft_accum_cplx(const int *pj, const int *pch, double *dft, const double *fr0,
+                     const double *fr1, int n, const double *ph, long long rstride, int nfreq,
+                     long long npts, void *stream);
 // sampling plan of one flux object (per point: the first Yee index, a 16-bit selector, the
 // palette bytes and the doubles of the chi1inv of its implicit-E values; see
 // dft_plan_kernel), then the sample of one update of every flux object due (one launch)
@@ -637,5 +641,8 @@ int k_copy(double *dst, const double *src, long long n, void *stream);
 int k_fill(double *p, double v, size_t n, void *stream);
 // the periodic ghost planes of the listed arrays (thread table: wrap_plan, mnl_wrap.hpp)
 int k_wrap(const WrapArgs &w, void *stream);
+// complex fields: the ghost planes of the listed pairs of arrays (part 0, part 1) times their
+// Bloch phases
+int k_wrap_phase(const WrapPhaseArgs &A, void *stream);
 
 }  // namespace mnl

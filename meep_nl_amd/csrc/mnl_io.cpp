@@ -1087,6 +1087,10 @@ int restore_magnetic(mnl_fields *F, MagBackup &bk) {
 int energy_in_box(mnl_fields *F, int which, const double wmin[3], const double wmax[3],
                   double *out) {
   if (F->fused && set_fused(F, false)) return -1;  // materialise implicit E
+  if (is_complex(F)) {  // both parts in the same mode: the wraps below list the arrays of both
+    mnl_fields *O = F->part0 ? F->part0 : F->twin.get();
+    if (O->fused && set_fused(O, false)) return -1;
+  }
   if (which == 0) return energy_of_type(F, T_E, wmin, wmax, out);
   if (which == 1) return energy_of_type(F, T_H, wmin, wmax, out);
   MagBackup bk;
@@ -1094,6 +1098,9 @@ int energy_in_box(mnl_fields *F, int which, const double wmin[3], const double w
   if (sync_magnetic(F, bk)) return -1;
   const int r = energy_of_type(F, T_H, wmin, wmax, &mag);
   if (restore_magnetic(F, bk) || r) return -1;
+  // complex fields: the synchronisation's wrap wrote the B / H ghost planes of both parts from
+  // one advanced and one unadvanced part; with the owners restored, wrap them again
+  if (is_complex(F) && wrap(F, 1)) return -1;
   if (energy_of_type(F, T_E, wmin, wmax, &el)) return -1;
   *out = el + mag;
   return 0;

@@ -401,6 +401,50 @@ int k_dft_accum(const int *pj, const int *pch, double *dft, const double *fr, in
   return rc();
 }
 
+// Complex fields: the numcmp == 2 branch of dft_chunk::update_dft
+// (src/dft.cpp:295-299), dft += phase * (f_re + i f_im) per update in update order, each
+// product as std::complex forms it (two products and one sum per part, no contraction).  fr0 /
+// fr1: the buffered sample rows of part 0 / part 1 (the same slots).  One thread per point;
+// launched only for complex fields, so the real path's kernel and bits do not move.
+__global__ void __launch_bounds__(256)
+    dft_accum_cplx_kernel(const int *__restrict__ pj, const int *__restrict__ pch,
+                          double2 *__restrict__ dft, const double *__restrict__ fr0,
+                          const double *__restrict__ fr1, int n, const double2 *__restrict__ ph,
+                          long long rstride, int nfreq, long long npts) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npts || pj[3 * p] < 0) return;
+  const double2 *__restrict__ php = ph + (long long)pch[p] * nfreq;
+  double a[DFT_KB], b[DFT_KB];
+#pragma unroll
+  for (int u = 0; u < DFT_KB; u++) {
+    a[u] = u < n ? fr0[u * npts + p] : 0.0;
+    b[u] = u < n ? fr1[u * npts + p] : 0.0;
+  }
+  double2 *__restrict__ dp = dft + (p >> 6) * nfreq * 64 + (p & 63);
+  for (int i = 0; i < nfreq; i++) {
+    double2 v = dp[(long long)i * 64];
+#pragma unroll
+    for (int u = 0; u < DFT_KB; u++) {
+      if (u < n) {
+        const double2 q = php[u * rstride + i];
+        v.x = v.x + (q.x * a[u] - q.y * b[u]);
+        v.y = v.y + (q.x * b[u] + q.y * a[u]);
+      }
+    }
+    dp[(long long)i * 64] = v;
+  }
+}
+
+int k_dft_accum_cplx(const int *pj, const int *pch, double *dft, const double *fr0,
+                     const double *fr1, int n, const double *ph, long long rstride, int nfreq,
+                     long long npts, void *stream) {
+  if (npts <= 0 || n <= 0) return 0;
+  if (n > DFT_KB || nfreq < 1 || !fr0 || !fr1) return 2;
+  dft_accum_cplx_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      pj, pch, (double2 *)dft, fr0, fr1, n, (const double2 *)ph, rstride, nfreq, npts);
+  return rc();
+}
+
 // ------------------------------------------------- DFT data in list order
 // get / load / scale of the DFT values (save_dft_hdf5 / load_dft_hdf5 / dft_chunk::scale_dft,
 // src/dft.cpp:401-496).  The array is [slot/64][freq][slot%64]; the public order is the

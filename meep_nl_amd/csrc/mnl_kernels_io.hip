@@ -1,6 +1,7 @@
 // mnl_kernels_io.hip -- gfx950 kernels behind mnl_io.cpp and the ABI's getters: the energy
 // integral, device layout -> a box of the whole-cell array (and the canonical layout), and the
-// elementwise average / copy / fill, and the periodic ghost wrap, with their launchers.
+// elementwise average / copy / fill, and the periodic ghost wrap (real fields, and complex
+// fields with their Bloch phases), with their launchers.
 #include "mnl_device.hpp"
 
 namespace mnl {
@@ -184,6 +185,55 @@ int k_wrap(const WrapArgs &w, void *stream) {
     if (w.per[a] && w.N[a] < 2) return 2;
   const long long total = w.fstart[3] * w.n;
   wrap_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, total);
+  return rc();
+}
+
+// Complex fields: the same connections with the Bloch phase of
+// fields::process_incoming_chunk_data (src/step.cpp:173-197) over pairs of arrays (part 0 =
+// real, part 1 = imaginary).  Each thread classifies its points' phases as connect_the_chunks
+// does (src/boundaries.cpp:402-404): exactly 1 is a copy, exactly -1 a negation (multiplying by
+// (1, 0) would change the sign of a zero), anything else the complex product with two roundings
+// per part (the file is built without contraction).  Same thread table and access shapes as
+// wrap_kernel; sources are owned points of either part.  wrap_phase_apply: mnl_wrap.hpp.
+
+__global__ __launch_bounds__(256) void wrap_phase_kernel(WrapPhaseArgs A, long long total) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  int arr;
+  long long dst[2], src[2];
+  const int np = wrap_points(A.w, t, arr, dst, src);
+  if (np == 0) return;
+  double *p = A.w.a[arr].p, *q = A.q[arr];
+  const int sh = A.w.a[arr].sh;
+  if (np == 2 && dst[1] == dst[0] + 1 && src[1] == src[0] + 1 &&
+      (((unsigned long long)(p + dst[0]) | (unsigned long long)(p + src[0]) |
+        (unsigned long long)(q + dst[0]) | (unsigned long long)(q + src[0])) & 15ull) == 0) {
+    const double2 vr = *reinterpret_cast<const double2 *>(p + src[0]);
+    const double2 vi = *reinterpret_cast<const double2 *>(q + src[0]);
+    double2 re, im;
+    wrap_phase_apply(A.ph[wrap_phase_index(A.w, sh, dst[0])], vr.x, vi.x, re.x, im.x);
+    wrap_phase_apply(A.ph[wrap_phase_index(A.w, sh, dst[1])], vr.y, vi.y, re.y, im.y);
+    *reinterpret_cast<double2 *>(p + dst[0]) = re;
+    *reinterpret_cast<double2 *>(q + dst[0]) = im;
+    return;
+  }
+  for (int k = 0; k < np; k++) {
+    double re, im;
+    wrap_phase_apply(A.ph[wrap_phase_index(A.w, sh, dst[k])], p[src[k]], q[src[k]], re, im);
+    p[dst[k]] = re;
+    q[dst[k]] = im;
+  }
+}
+
+int k_wrap_phase(const WrapPhaseArgs &A, void *stream) {
+  const WrapArgs &w = A.w;
+  if (w.n <= 0 || w.n > WRAP_MAXA || w.fstart[3] <= 0) return w.n > WRAP_MAXA ? 2 : 0;
+  for (int a = 0; a < 3; a++)
+    if (w.per[a] && w.N[a] < 2) return 2;
+  for (int k = 0; k < w.n; k++)
+    if (!w.a[k].p || !A.q[k]) return 2;
+  const long long total = w.fstart[3] * w.n;
+  wrap_phase_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(A, total);
   return rc();
 }
 

@@ -13,6 +13,7 @@ namespace mnlh {
 // of `where` it stands for.
 struct CLoop {
   int isc[3], iec[3], shifti[3];
+  cplx ph = 1.0;  // the lattice shift's Bloch phase (src/loop_in_chunks.cpp:409-416)
   double s0[3], s1[3], e0[3], e1[3];
   double W(int d, long i) const {  // IVEC_LOOP_WEIGHT1x (src/meep/vec.hpp:372-378)
     const long n = (iec[d] - isc[d]) / 2 + 1;
@@ -22,7 +23,8 @@ struct CLoop {
 };
 
 static std::vector<CLoop> chunk_loops(const mnl_structure &S, const bool per[3], int c,
-                                      const double wmin[3], const double wmax[3]) {
+                                      const double wmin[3], const double wmax[3],
+                                      const cplx *eikna = nullptr) {
   int is[3] = {0, 0, 0}, ie[3] = {0, 0, 0};
   for (int d = 0; d < 3; d++) {
     if (!S.has[d]) continue;
@@ -36,8 +38,13 @@ static std::vector<CLoop> chunk_loops(const mnl_structure &S, const bool per[3],
   std::vector<CLoop> out;
   LatticeShifts ls(S, per, wmin, wmax);
   do {
+  cplx ph = 1.0;
+  if (eikna)  // complex fields: ph *= pow(eikna[d], ishift[d]) over the directions
+    for (int d = 0; d < 3; d++)
+      if (S.has[d]) ph *= pow(eikna[d], ls.cur[d]);
   for (auto &ch : reference_chunks(S)) {
     CLoop L;
+    L.ph = ph;
     bool emp = false;
     for (int d = 0; d < 3; d++) {
       L.s0[d] = L.s1[d] = L.e0[d] = L.e1[d] = 1.0;
@@ -129,7 +136,8 @@ static int add_volume_source(mnl_fields *F, int c, int st, const double wmin0[3]
   SrcGroup grp;
   grp.comp = c;
   grp.st = st;
-  for (const CLoop &L : chunk_loops(S, F->periodic, c, wmin, wmax)) {
+  for (const CLoop &L : chunk_loops(S, F->periodic, c, wmin, wmax,
+                                    is_complex(F) ? (F->part0 ? F->part0 : F)->eikna : nullptr)) {
     long ln[3];
     for (int k = 0; k < 3; k++) ln[k] = S.has[yd[k]] ? (L.iec[yd[k]] - L.isc[yd[k]]) / 2 + 1 : 1;
     for (long i1 = 0; i1 < ln[0]; i1++)
@@ -162,7 +170,7 @@ static int add_volume_source(mnl_fields *F, int c, int st, const double wmin0[3]
             afunc(rel, adata, &re, &im);
             A = cplx(re, im);
           }
-          grp.amp.push_back(wgt * (amp * std::conj(cplx(1.0))) * A);
+          grp.amp.push_back(wgt * (amp * std::conj(L.ph)) * A);  // src/sources.cpp:259
           grp.gidx.push_back(gi);
           for (int d = 0; d < 3; d++) grp.jglob.push_back(jg[d]);
         }
@@ -331,7 +339,10 @@ int build_source_lists(mnl_fields *F) {
       I2.push_back(I[k]);
       C2.push_back(C[k]);
       R2.push_back(R[k]);
-      const cplx a = F->groups[R[k].first].amp[R[k].second];
+      cplx a = F->groups[R[k].first].amp[R[k].second];
+      // part 1 of complex fields adds imag(a J) where part 0 adds real(a J) (src/step.cpp:
+      // 300-315): the kernel's real((a_i, -a_r) J) = a_i J_r + a_r J_i
+      if (F->part0) a = cplx(imag(a), -real(a));
       A.push_back(real(a));
       A.push_back(imag(a));
       Gd.push_back(R[k].first);

@@ -28,6 +28,7 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
     bool low_ghost;  // true: send top plane up, receive plane 0 from below
   };
   std::vector<Item> items;
+  auto gather = [&](const mnl_fields *F) {  // (shadows F: one part's arrays)
   for (int c = 0; c < 3; c++) {
     if (kind == 0) {
       if (c != sd && F->f.E[c] && F->allocated[c]) items.push_back({F->f.E[c], true});
@@ -53,6 +54,16 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
       for (int k = 0; k < F->f.npol; k++)
         if (F->f.pol[k].P[c]) items.push_back({F->f.pol[k].P[c], c != sd});
     }
+  }
+  };
+  // complex fields: both parts' arrays in one group, whichever part
+  // the call names (they share the communicator and the slab geometry)
+  if (is_complex(F)) {
+    mnl_fields *P = F->part0 ? F->part0 : F;
+    gather(P);
+    gather(P->twin.get());
+  } else {
+    gather(F);
   }
   if (items.empty()) return 0;
   Comm &cm = *F->comm;
@@ -81,12 +92,50 @@ int exchange(mnl_fields *F, int kind, hipStream_t st) {
 // per susceptibility, of which a structure takes MAX_POL -- one launch holds them all.
 constexpr int WRAP_FIELD_ARRAYS = 3 * 8;  // per direction: E, f_w, Bn, Hn, B, H, D, Dn (the add() calls below)
 static_assert(WRAP_FIELD_ARRAYS + 3 * MAX_POL <= WRAP_MAXA, "wrap(WRAP_ALL) must fit one launch");
+static int wrap_list(mnl_fields *F, int kind, WrapArgs &w);
+static int wrap_cplx(mnl_fields *F, int kind, hipStream_t st);
+
 int wrap(mnl_fields *F, int kind, hipStream_t st) {
   if (!any_periodic(F)) return 0;
+  if (is_complex(F)) return wrap_cplx(F->part0 ? F->part0 : F, kind, st);
   if (!st) st = F->stream;
+  WrapArgs w{};
+  if (wrap_list(F, kind, w)) return -1;
+  if (w.n == 0) return 0;
+  wrap_plan(w);
+  if (k_wrap(w, st)) return fail("periodic wrap launch failed");
+  return 0;
+}
+
+// Complex fields: one launch for both parts, every ghost point times
+// its Bloch phase (fields::process_incoming_chunk_data, src/step.cpp:173-197).  Both parts
+// list the same arrays in the same order: they have the same structure and step in the same
+// mode.
+static int wrap_cplx(mnl_fields *F, int kind, hipStream_t st) {
+  mnl_fields *T = F->twin.get();
+  if (!st) st = F->stream;
+  WrapPhaseArgs A{};
+  WrapArgs w1{};
+  if (wrap_list(F, kind, A.w) || wrap_list(T, kind, w1)) return -1;
+  if (A.w.n != w1.n) return fail("periodic wrap: the parts of the complex fields differ");
+  if (A.w.n == 0) return 0;
+  for (int i = 0; i < w1.n; i++) {
+    if (A.w.a[i].sh != w1.a[i].sh) return fail("periodic wrap: the parts of the complex fields differ");
+    A.q[i] = w1.a[i].p;
+  }
+  int dir_of_axis[3] = {-1, -1, -1};
+  for (int d = 0; d < 3; d++)
+    if (F->g.ax[d] >= 0) dir_of_axis[F->g.ax[d]] = d;
+  bloch_phase_table(F->eikna, dir_of_axis, A.ph);
+  wrap_plan(A.w);
+  if (k_wrap_phase(A, st)) return fail("periodic wrap launch failed");
+  return 0;
+}
+
+// the arrays of one wrap kind (no launch)
+static int wrap_list(mnl_fields *F, int kind, WrapArgs &w) {
   const DevGrid &g = F->g;
   const DevFields &f = F->f;
-  WrapArgs w{};
   for (int k = 0; k < 3; k++) w.N[k] = g.N[k], w.st[k] = g.st[k];
   for (int d = 0; d < 3; d++)
     if (g.ax[d] >= 0 && F->periodic[d]) w.per[g.ax[d]] = 1;
@@ -119,9 +168,6 @@ int wrap(mnl_fields *F, int kind, hipStream_t st) {
     }
   }
   if (full) return fail("periodic wrap: too many arrays");
-  if (w.n == 0) return 0;
-  wrap_plan(w);
-  if (k_wrap(w, st)) return fail("periodic wrap launch failed");
   return 0;
 }
 
@@ -130,6 +176,12 @@ int wrap(mnl_fields *F, int kind, hipStream_t st) {
 // materialises E; the next batch enters it again.
 int wrap_for_readers(mnl_fields *F) {
   if (!any_periodic(F)) return 0;
+  if (is_complex(F)) {  // both parts leave the mode: the wrap lists the same arrays of each
+    mnl_fields *P = F->part0 ? F->part0 : F;
+    for (mnl_fields *p : {P, P->twin.get()})
+      if (p->fused && set_fused(p, false)) return -1;
+    return wrap(P, WRAP_ALL);
+  }
   if (F->fused && set_fused(F, false)) return -1;
   return wrap(F, WRAP_ALL);
 }
@@ -516,7 +568,7 @@ static int source_table(mnl_fields *F, long long t0, int ns, const SrcRow &row) 
     for (size_t k = 0; k < nI; k++) {
       const SrcGroup &G = F->groups[F->isrc_ref[k].first];
       const cplx A = G.amp[F->isrc_ref[k].second] * F->srcs[G.st].cur_dipole;
-      vI[k] = real(A);
+      vI[k] = F->part0 ? imag(A) : real(A);  // part 1 of complex fields: the imaginary part
     }
   }
   size_t bytes = vals.size() * sizeof(double);
@@ -602,11 +654,15 @@ static int fused_interior(mnl_fields *F, const ISrcDev &is, PhaseTimer &pt, int 
 
 // One step (step s of the chunk), one launch sequence per phase of fields::step
 // (src/step.cpp:35-140): unfused, or fused on one rank.
+// Its three parts, between which the ghost planes are made valid: step_one runs them on one
+// field set, step_one_cplx on the two parts of complex fields.
+static int step_one_bh(mnl_fields *F, const SrcDev &sB, const ISrcDev &is, PhaseTimer &pt,
+                       bool *nr_done);
+static int step_one_de(mnl_fields *F, const SrcDev &sD, const ISrcDev &is, PhaseTimer &pt,
+                       bool nr_done);
+
 static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, const ISrcDev &is,
                     PhaseTimer &pt) {
-  DevFields &f = F->f;
-  const DevGrid &g = F->g;
-  const int nB = sB.n, nD = sD.n, nI = is.n;
   // ---- B: halo of E (low ghost), curl, sources
   if (!F->u_first_done[0] && u_lazy_copy(F, 0)) return -1;
   if (F->nranks > 1) {
@@ -619,9 +675,71 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
     if (wrap(F, 0)) return -1;
     pt.end(k);
   }
+  bool nr_done = false;  // the NR box's E phase already launched (beside the tile kernel)
+  if (step_one_bh(F, sB, is, pt, &nr_done)) return -1;
+  if (F->nranks > 1) {
+    int kk = pt.begin(TM_HALO);
+    if (exchange(F, 1)) return fail("H halo exchange failed");
+    pt.end(kk);
+  }
+  if (any_periodic(F)) {
+    int kk = pt.begin(TM_HALO);
+    if (wrap(F, 1)) return -1;
+    pt.end(kk);
+  }
+  if (step_one_de(F, sD, is, pt, nr_done)) return -1;
+  if (post_step(F, pt, s)) return -1;
+  return step_guard(F, s);
+}
+
+// One step of complex fields (one rank, or unfused on several): each part of the step on part 0, then on part 1 (one
+// stream), then the phased wrap of both, then the DFT samples of both.
+static int step_one_cplx(mnl_fields *const P[2], int s, const SrcDev sB[2], const SrcDev sD[2],
+                         const ISrcDev is[2], PhaseTimer &pt) {
+  mnl_fields *F = P[0];
+  for (int p = 0; p < 2; p++)
+    if (!P[p]->u_first_done[0] && u_lazy_copy(P[p], 0)) return -1;
+  // several ranks (unfused): one exchange lists both parts' planes, then the rank-local wrap
+  if (F->nranks > 1 || any_periodic(F)) {
+    int k = pt.begin(TM_HALO);
+    if (F->nranks > 1 && exchange(F, 0)) return fail("E halo exchange failed");
+    if (wrap(F, 0)) return -1;
+    pt.end(k);
+  }
+  bool nr_done = false;
+  for (int p = 0; p < 2; p++)
+    if (step_one_bh(P[p], sB[p], is[p], pt, &nr_done)) return -1;
+  if (F->nranks > 1 || any_periodic(F)) {
+    int k = pt.begin(TM_HALO);
+    if (F->nranks > 1 && exchange(F, 1)) return fail("H halo exchange failed");
+    if (wrap(F, 1)) return -1;
+    pt.end(k);
+  }
+  for (int p = 0; p < 2; p++)
+    if (step_one_de(P[p], sD[p], is[p], pt, false)) return -1;
+  // fields::update_dfts: both parts sample a row (part 1 first: part 0's update accumulates
+  // the rows of both once its buffer is full, dft_flush)
+  if (dft_due(F, F->t + s + 1)) {
+    if (F->nranks > 1 && (exchange(F, 0) || exchange(F, 3))) return fail("DFT halo exchange failed");
+    if (wrap(F, 0) || wrap(F, 3)) return -1;
+    const int k = pt.begin(TM_DFT);
+    const int r = dft_update(P[1], P[1]->t + s + 1) || dft_update(F, F->t + s + 1);
+    pt.end(k);
+    if (r) return -1;
+  }
+  for (int p = 0; p < 2; p++)
+    if (step_guard(P[p], s)) return -1;
+  return 0;
+}
+
+static int step_one_bh(mnl_fields *F, const SrcDev &sB, const ISrcDev &is, PhaseTimer &pt,
+                       bool *nr_done_out) {
+  DevFields &f = F->f;
+  const DevGrid &g = F->g;
+  const int nB = sB.n;
   const BoxList *sl = F->fused ? &F->fused_shell : &F->shell_list;
   int k = pt.begin(TM_BINT);
-  bool nr_done = false;  // the NR box's E phase already launched (beside the tile kernel)
+  bool &nr_done = *nr_done_out;
   if (F->fused) {
     if (fused_interior(F, is, pt, k, &nr_done)) return -1;
   } else if (k_curl(T_B, F->interior, nullptr, g, f, F->planB, F->S.courant, F->stream)) {
@@ -645,19 +763,19 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
   k = (!fuseH && anyH && (shell_work || F->hall)) ? pt.begin(TM_H) : -1;
   if (!fuseH && update_h_any(F, *sl, true)) return -1;
   pt.end(k);
-  if (F->nranks > 1) {
-    int kk = pt.begin(TM_HALO);
-    if (exchange(F, 1)) return fail("H halo exchange failed");
-    pt.end(kk);
-  }
-  if (any_periodic(F)) {
-    int kk = pt.begin(TM_HALO);
-    if (wrap(F, 1)) return -1;
-    pt.end(kk);
-  }
+  return 0;
+}
+
+static int step_one_de(mnl_fields *F, const SrcDev &sD, const ISrcDev &is, PhaseTimer &pt,
+                       bool nr_done) {
+  DevFields &f = F->f;
+  const DevGrid &g = F->g;
+  const int nD = sD.n, nI = is.n;
+  const BoxList *sl = F->fused ? &F->fused_shell : &F->shell_list;
+  const bool shell_work = sl->n > 0 && sl->start[sl->n] > 0;
   // ---- D
   if (!F->u_first_done[1] && u_lazy_copy(F, 1)) return -1;
-  k = !F->fused ? pt.begin(TM_DINT) : -1;
+  int k = !F->fused ? pt.begin(TM_DINT) : -1;
   if (!F->fused && k_curl(T_D, F->interior, nullptr, g, f, F->planD, F->S.courant, F->stream))
     return fail("curl D launch failed");
   pt.end(k);
@@ -718,11 +836,63 @@ static int step_one(mnl_fields *F, int s, const SrcDev &sB, const SrcDev &sD, co
     pt.end(k);
   }
   if (F->fused) swap_cur_nxt(f);
-  if (post_step(F, pt, s)) return -1;
-  return step_guard(F, s);
+  return 0;
+}
+
+// step_batch for complex fields: both parts prepared, then stepped in lockstep one step at a
+// time (no pairs of steps); each part has its own source table (part 1's amplitudes are -i times
+// part 0's, so that it adds imag(A J) where part 0 adds real(A J), src/step.cpp:300-315) and
+// its own NaN guard.
+static int step_batch_cplx(mnl_fields *F, int nsteps) {
+  mnl_fields *const P[2] = {F, F->twin.get()};
+  for (mnl_fields *p : P) {
+    if (p->src_dirty && build_source_lists(p)) return -1;
+    p->tb_last = false;
+  }
+  // the same mode for both; several ranks step complex fields unfused
+  const bool fuse = F->nranks == 1 && fused_agreed(P[0]) && fused_agreed(P[1]);
+  for (mnl_fields *p : P) {
+    if (set_fused(p, fuse)) return -1;
+    dsrc_in_shell_scan(p);
+    if (nan_terms_build(p)) return -1;
+  }
+  if (P[0]->fused != P[1]->fused)
+    return fail("complex fields: the two parts did not enter the same stepping mode");
+  const SrcRow row[2] = {SrcRow(P[0]), SrcRow(P[1])};
+  PhaseTimer pt(F);
+  for (int s0 = 0; s0 < nsteps; s0 += NAN_CH) {
+    const int ns = std::min(NAN_CH, nsteps - s0);
+    for (int p = 0; p < 2; p++) {
+      if (!P[p]->dfts.empty() && dft_prepare(P[p], P[p]->t, ns)) return -1;
+      if (source_table(P[p], P[p]->t, ns, row[p])) return -1;
+    }
+    for (int s = 0; s < ns; s++) {
+      SrcDev sB[2], sD[2];
+      ISrcDev is[2];
+      for (int p = 0; p < 2; p++) {
+        P[p]->f.nr_t = P[p]->t + s;
+        const double *vs = P[p]->d_vals + (size_t)s * row[p].per;
+        sB[p] = src_dev(P[p], 0, vs), sD[p] = src_dev(P[p], 1, vs + 2 * row[p].ng);
+        is[p] = P[p]->isrc_dev;
+        is[p].n = (int)row[p].nI;
+        is[p].val = vs + row[p].jofs;
+      }
+      if (step_one_cplx(P, s, sB, sD, is, pt)) return -1;
+    }
+    for (mnl_fields *p : P) p->t += ns;
+    if (pt.flush() != 0) return -1;
+    for (mnl_fields *p : P)
+      if (nan_result(p)) return -1;
+  }
+  for (mnl_fields *p : P)
+    if (p->s_aux) HIPCHK(hipStreamSynchronize(p->s_aux));
+  HIPCHK(hipStreamSynchronize(F->stream));
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 static int step_batch(mnl_fields *F, int nsteps) {
+  if (F->twin) return step_batch_cplx(F, nsteps);
   if (F->src_dirty && build_source_lists(F)) return -1;
   if (set_fused(F, fused_agreed(F))) return -1;
   dsrc_in_shell_scan(F);
@@ -912,14 +1082,18 @@ int fields_step(mnl_fields *F, int nsteps) {
 static int fields_step_batches(mnl_fields *F, int nsteps) {
   while (nsteps > 0) {
     int m;
+    mnl_fields *T = F->twin.get();  // complex fields: part 1 takes its first step with part 0
+    if (T && T->force_unfused_next) F->force_unfused_next = true;
     if (!F->e_first_done || !F->h_first_done || !F->u_first_done[0] || !F->u_first_done[1] ||
         F->force_unfused_next) {
       const bool saved = F->allow_fused;
       F->allow_fused = false;
       F->first_step_mode = true;
+      if (T) T->allow_fused = false, T->first_step_mode = true;
       const int r = step_batch(F, 1);
       F->allow_fused = saved;
       F->first_step_mode = false;
+      if (T) T->allow_fused = saved, T->first_step_mode = false, T->force_unfused_next = false;
       if (r) return -1;
       F->force_unfused_next = false;
       m = 1;

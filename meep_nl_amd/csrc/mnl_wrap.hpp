@@ -95,4 +95,41 @@ MNL_HD inline int wrap_points(const WrapArgs &w, long long t, int &arr, long lon
   return np;
 }
 
+// Complex fields: the same threads over pairs of arrays (part 0, part 1)
+// with the Bloch phase of every ghost point.  ph: the host's table (mnl_bloch.hpp), indexed by
+// {none, low, high} per device axis.
+struct WrapPhaseArgs {
+  WrapArgs w;               // w.a[k].p: part 0
+  double *q[WRAP_MAXA];     // part 1
+  double ph[27][2];
+};
+
+// One ghost value: the phase classified as connect_the_chunks does (src/boundaries.cpp:402-404)
+// -- exactly 1 is a copy, exactly -1 a negation, anything else the complex product of
+// fields::process_incoming_chunk_data (src/step.cpp:188-193), two roundings per part (both
+// compilers build this without contraction).
+MNL_HD inline void wrap_phase_apply(const double ph[2], double vr, double vi, double &re,
+                                    double &im) {
+  const double pr = ph[0], pi = ph[1];
+  if (pr == 1.0 && pi == 0.0) {
+    re = vr, im = vi;
+  } else if (pr == -1.0 && pi == 0.0) {
+    re = -vr, im = -vi;
+  } else {
+    re = pr * vr - pi * vi;
+    im = pr * vi + pi * vr;
+  }
+}
+
+// the phase-table index of destination point dst of an array with shift mask sh: along every
+// periodic axis on whose not-owned plane it lies, 1 (plane 0, brought in from below) or 2
+// (plane n, from above)
+MNL_HD inline int wrap_phase_index(const WrapArgs &w, int sh, long long dst) {
+  const int j[3] = {(int)(dst % w.st[1]), (int)((dst % w.st[2]) / w.st[1]), (int)(dst / w.st[2])};
+  int idx = 0, m = 1;
+  for (int a = 0; a < 3; a++, m *= 3)
+    if (w.per[a] && j[a] == wrap_ghost(w, sh, a)) idx += m * (((sh >> a) & 1) ? 2 : 1);
+  return idx;
+}
+
 }  // namespace mnl

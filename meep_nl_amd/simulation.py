@@ -1144,10 +1144,13 @@ _WARNED_AVERAGING = False
 
 
 class Simulation:
+    complex_fields = False  # real fields unless the constructor is told otherwise
+
     def __init__(self, cell_size, resolution, geometry=(), sources=(), boundary_layers=(),
                  default_material=Medium(), Courant=0.5, eps_averaging=True, dimensions=None,
                  force_complex_fields=False, k_point=False, symmetries=(), parallel=None,
-                 nonlinear_mode="fork", progress_interval=4, time_phases=True, **kwargs):
+                 nonlinear_mode="fork", progress_interval=4, time_phases=True,
+                 complex_fields=False, **kwargs):
         self.cell_size = Vector3(*cell_size)
         self.resolution = float(resolution)
         self.geometry = list(geometry)
@@ -1166,6 +1169,10 @@ class Simulation:
                 dimensions = 1
         self.dimensions = dimensions
         self.k_point = k_point
+        # a project keyword like nonlinear_mode: complex fields (fields::use_real_fields not
+        # called), with which a non-zero k_point is accepted; k_point=Vector3() then gives
+        # complex fields at k = 0, Meep's force_complex_fields
+        self.complex_fields = bool(complex_fields)
         self.periodic_directions = self._periodic_directions()
         self.parallel = parallel
         # "upstream": Meep's Pade chi2/chi3 E update instead of the fork's (an
@@ -1188,9 +1195,9 @@ class Simulation:
         the PML."""
         if self.k_point is False or self.k_point is None:
             return ()
-        if Vector3(*self.k_point) != Vector3():
+        if Vector3(*self.k_point) != Vector3() and not self.complex_fields:
             raise NotImplementedError(
-                "a non-zero k_point needs complex fields, which are out of scope "
+                "a non-zero k_point needs complex fields: pass complex_fields=True "
                 "(k_point=Vector3() gives periodic boundaries with real fields)")
         if self.dimensions == 1:
             raise RuntimeError("meep: use_bloch: periodic boundaries of 1-D cells are not "
@@ -1406,8 +1413,12 @@ class Simulation:
             self.fields = core.Fields(self.structure)
         # per-phase GPU times for print_times (HIP events; ~0.3 % of a step)
         self.fields.set_profiling(self.time_phases)
+        if self.complex_fields:
+            self.fields.use_complex_fields()
         for d in self.periodic_directions:  # before the sources: their image chunks
-            self.fields.use_bloch(d)
+            k = Vector3(*self.k_point)[d] if self.complex_fields else 0
+            # Simulation's k_point is in units of 2 pi / length like fields::use_bloch's
+            self.fields.use_bloch(d, k)
         for src in self.sources:
             src.add_source(self.fields)
         if getattr(self, "load_fields_file", None):  # delayed load (python/simulation.py:2509-2510)
@@ -1485,7 +1496,10 @@ class Simulation:
                     batch *= 2
             self._run_finished()
             return
-        if not step_funcs and all(isinstance(c, (numbers.Number, _Condition)) for c in conds):
+        # (complex fields have no probes yet: their conditions go through the one-step loop)
+        if not step_funcs and not (self.complex_fields and
+                                   any(isinstance(c, _Condition) for c in conds)) and all(
+                isinstance(c, (numbers.Number, _Condition)) for c in conds):
             self._run_until_batched(conds, t0)
             return
         for i, c in enumerate(conds):
@@ -1945,17 +1959,21 @@ class Simulation:
     # -- monitors
     def get_field_point(self, c, pt):
         self.init_sim()
+        if self.complex_fields:
+            return self.fields.get_field_complex(c, tuple(pt))
         return self.fields.get_field(c, tuple(pt))
 
     def get_array(self, component=Ez, vol=None, center=None, size=None, cmplx=None, arr=None,
                   frequency=0, snap=False):
         """Simulation.get_array (python/simulation.py:3872-3990) ->
         fields::get_array_slice over the volume (default: the whole cell) on the
-        Centered grid, empty dimensions interpolated and collapsed.  Real fields
-        only; snap=True snaps empty dimensions to the nearest grid point."""
+        Centered grid, empty dimensions interpolated and collapsed.  The real
+        part, or with cmplx=True on complex fields a complex array; snap=True snaps empty
+        dimensions to the nearest grid point."""
         self.init_sim()
-        if cmplx or frequency:
-            raise NotImplementedError("get_array: complex / frequency-dependent slices")
+        if frequency or (cmplx and not self.complex_fields):
+            raise NotImplementedError("get_array: frequency-dependent slices, and complex "
+                                      "slices of real fields")
         if vol is not None:
             center, size = vol.center, vol.size
         center = Vector3(*(center if center is not None else Vector3()))
@@ -1965,7 +1983,7 @@ class Simulation:
         for d in dirs:
             lo[d] = center[d] - 0.5 * size[d]
             hi[d] = center[d] + 0.5 * size[d]
-        out = self.fields.get_array_slice(component, lo, hi, snap)
+        out = self.fields.get_array_slice(component, lo, hi, snap, cmplx=bool(cmplx))
         if arr is not None:
             arr[...] = out
             return arr
