@@ -570,6 +570,40 @@ int mnl_fields_probe_read(mnl_fields *f, int handle, long long cap, long long *c
 int mnl_fields_probe_reset(mnl_fields *f, int handle);
 int mnl_fields_remove_probe(mnl_fields *f, int handle);
 int mnl_fields_remove_probes(mnl_fields *f);
+/* ---- LDOS spectra: dft_ldos (src/dft_ldos.cpp) ------------------------------------------------
+ * The power spectrum of the sources normalised to the local density of states.  An update sums
+ * E conj(A) over the points of every electric source volume and H conj(A) over those of every
+ * magnetic one (A: the source's amplitude at the point), Fourier-transforms the two sums and
+ * the current of the first source; the sums run on the device inside whatever stepping mode is
+ * active.  The point lists follow the sources: when sources are added,
+ * removed or changed, what is buffered is accumulated with the old lists first.  Real fields
+ * only.  LDOS objects are not DFT objects: they have their own handles and do not enter
+ * mnl_fields_dft_norm / dft_maxfreq / max_decimation or mnl_fields_dump; after mnl_fields_load
+ * or mnl_fields_set_time the updates still buffered are dropped.
+ * mnl_fields_add_ldos replaces dft_ldos::dft_ldos(freq, Nfreq). */
+int mnl_fields_add_ldos(mnl_fields *f, const double *freqs, int nfreq, int *handle);
+/* Replaces dft_ldos::update(fields&): one update of the current state. */
+int mnl_fields_ldos_update(mnl_fields *f, int handle);
+/* on != 0: from now on every step appends the update of the state after it (what calling
+ * mnl_fields_ldos_update after every single step does, without leaving the batch); on == 0:
+ * no longer.  Updates are buffered and accumulated in blocks; every reader accumulates first. */
+int mnl_fields_ldos_record(mnl_fields *f, int handle, int on);
+/* Replaces dft_ldos::ldos() / F() / J() / overall_scale() (src/dft_ldos.cpp:60-95): ldos[nfreq],
+ * F[2 nfreq] and J[2 nfreq] as (re, im), *overall_scale; any output may be NULL.  Before the
+ * first update ldos is NaN, as the reference's.  Distributed: collective; F is summed over the
+ * ranks and the formula applied to the sum. */
+int mnl_fields_ldos_data(mnl_fields *f, int handle, double *ldos, double *F, double *J,
+                         double *overall_scale);
+/* Diagnostic (as mnl_fields_dft_points): the global point list in list order, the electric
+ * sources' points, then the magnetic ones'.  *n points; with comp / ijk / amp given (each may be
+ * NULL) and cap >= *n: the field component sampled, the point's 3 global indices on that
+ * component's grid, the amplitude A as (re, im). */
+int mnl_fields_ldos_points(mnl_fields *f, int handle, long long cap, long long *n, int *comp,
+                           int *ijk, double *amp);
+/* Remove one LDOS object (the others keep their handles) / every one; buffered updates are
+ * dropped with it. */
+int mnl_fields_remove_ldos(mnl_fields *f, int handle);
+int mnl_fields_remove_ldoses(mnl_fields *f);
 /* fields::dft_norm() (src/dft.cpp:312-361): the square root of the sum of |dft|^2 over every
  * frequency and point of every chunk list of every DFT object (flux, fields, near2far, energy,
  * force; not probes), reduced on the device in a fixed order and summed over the ranks

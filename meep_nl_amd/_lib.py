@@ -130,6 +130,13 @@ _SIGS = {
     "mnl_fields_probe_reset": (c_int, [c_void, c_int]),
     "mnl_fields_remove_probe": (c_int, [c_void, c_int]),
     "mnl_fields_remove_probes": (c_int, [c_void]),
+    "mnl_fields_add_ldos": (c_int, [c_void, dptr, c_int, iptr]),
+    "mnl_fields_ldos_update": (c_int, [c_void, c_int]),
+    "mnl_fields_ldos_record": (c_int, [c_void, c_int, c_int]),
+    "mnl_fields_ldos_data": (c_int, [c_void, c_int, dptr, dptr, dptr, dptr]),
+    "mnl_fields_ldos_points": (c_int, [c_void, c_int, ctypes.c_longlong, llptr, iptr, iptr, dptr]),
+    "mnl_fields_remove_ldos": (c_int, [c_void, c_int]),
+    "mnl_fields_remove_ldoses": (c_int, [c_void]),
     "mnl_fields_dft_norm": (c_int, [c_void, dptr]),
     "mnl_fields_dft_maxfreq": (c_int, [c_void, dptr]),
     "mnl_fields_max_decimation": (c_int, [c_void, iptr]),

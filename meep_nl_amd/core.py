@@ -806,6 +806,60 @@ class Fields:
     def remove_probes(self):
         check(lib().mnl_fields_remove_probes(self.h))
 
+    # -- LDOS spectra (dft_ldos)
+    def add_ldos(self, freqs):
+        """dft_ldos(freq): an LDOS object over the current and future sources; returns its
+        handle (not a DFT handle)."""
+        freqs = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.float64)
+        h = ctypes.c_int()
+        check(lib().mnl_fields_add_ldos(self.h, ptr(freqs), int(freqs.size), ctypes.byref(h)))
+        self._ldos_nfreq = getattr(self, "_ldos_nfreq", {})
+        self._ldos_nfreq[h.value] = int(freqs.size)
+        return h.value
+
+    def ldos_update(self, h):
+        """dft_ldos::update(fields): one update of the current state."""
+        check(lib().mnl_fields_ldos_update(self.h, h))
+
+    def ldos_record(self, h, on):
+        """While on, every step appends the update of the state after it (on the device, in
+        whatever stepping mode is active)."""
+        check(lib().mnl_fields_ldos_record(self.h, h, 1 if on else 0))
+
+    def ldos_data(self, h):
+        """(ldos[nfreq], F[nfreq] complex, J[nfreq] complex, overall_scale): dft_ldos::ldos(),
+        F(), J() and overall_scale() (collective; buffered updates are accumulated first)."""
+        nf = getattr(self, "_ldos_nfreq", {}).get(h, 1)
+        ld = np.zeros(nf, dtype=np.float64)
+        F = np.zeros(2 * nf, dtype=np.float64)
+        J = np.zeros(2 * nf, dtype=np.float64)
+        s = ctypes.c_double()
+        check(lib().mnl_fields_ldos_data(self.h, h, ptr(ld), ptr(F), ptr(J), ctypes.byref(s)))
+        return ld, F[0::2] + 1j * F[1::2], J[0::2] + 1j * J[1::2], s.value
+
+    def ldos_points(self, h):
+        """(comp[n], ijk[n, 3], amp[n] complex): the object's global point list in list order,
+        the electric sources' points, then the magnetic ones' (a diagnostic)."""
+        n = ctypes.c_longlong()
+        check(lib().mnl_fields_ldos_points(self.h, h, 0, ctypes.byref(n), None, None, None))
+        m = max(n.value, 1)
+        comp = np.zeros(m, dtype=np.int32)
+        ijk = np.zeros(3 * m, dtype=np.int32)
+        amp = np.zeros(2 * m, dtype=np.float64)
+        check(lib().mnl_fields_ldos_points(
+            self.h, h, m, ctypes.byref(n), comp.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+            ijk.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ptr(amp)))
+        k = n.value
+        return comp[:k], ijk[:3 * k].reshape(k, 3), (amp[0::2] + 1j * amp[1::2])[:k]
+
+    def remove_ldos(self, h):
+        check(lib().mnl_fields_remove_ldos(self.h, h))
+        getattr(self, "_ldos_nfreq", {}).pop(h, None)
+
+    def remove_ldoses(self):
+        check(lib().mnl_fields_remove_ldoses(self.h))
+        self._ldos_nfreq = {}
+
     def dft_norm(self):
         """fields::dft_norm(): sqrt of the sum of |dft|^2 over every DFT object (collective)."""
         v = ctypes.c_double()

@@ -934,6 +934,7 @@ int dft_prepare(mnl_fields *F, long long t0, int ns) {
 int dft_flush(mnl_fields *F, DftFluxH &o) {
   if (!o.nbuf) return 0;
   if (o.kind == DFT_PROBE) return probe_flush(F, o);
+  if (o.kind == DFT_LDOS) return ldos_flush(F, o);
   const size_t nch = dft_nchunks(o);
   const long long rstride = (long long)(nch * o.nfreq);
   // Complex fields: part 1's object only samples; its rows are
@@ -975,9 +976,10 @@ long long dft_plan_key(const mnl_fields *F) {
 // step of a pair from the mid set)
 // cstate >= 0: a pair's middle (0) or new (1) state, whose two-step points are also in the
 // monitors' compact boxes
-int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) {
+int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate, DftFluxH *only) {
   const bool planned = F->nlocal < (size_t(1) << 31);  // int32 indices in the plan
   const DevFields &fs = fields ? *fields : F->f;
+  auto skip = [&](const DftFluxH &o) { return only ? &o != only || !o.npts : !dft_samples_at(o, t); };
   // the samples of every flux object due: planned ones in merged launches of up to DFT_MAXJ
   DftSampleJobs J{};
   auto launch = [&]() -> int {
@@ -988,7 +990,7 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
   };
   for (DftFluxH *op : F->sampled) {
     DftFluxH &o = *op;
-    if (t % o.decim || !o.npts) continue;
+    if (skip(o)) continue;
     double *fr = o.d_fr + (size_t)o.nbuf * o.npts;
     if (planned) {
       const long long key = dft_plan_key(F);
@@ -1040,9 +1042,10 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
   if (launch()) return -1;
   for (DftFluxH *op : F->sampled) {
     DftFluxH &o = *op;
-    if (t % o.decim || !o.npts) continue;
+    if (skip(o)) continue;
     o.nbuf++;
     o.row++;
+    if (o.kind == DFT_LDOS) ldos_sampled(F, o);
     if (o.nbuf == o.kb && dft_flush(F, o)) return -1;
   }
   return 0;
@@ -1050,7 +1053,7 @@ int dft_update(mnl_fields *F, long long t, const DevFields *fields, int cstate) 
 
 bool dft_due(const mnl_fields *F, long long t) {
   for (DftFluxH *op : F->sampled)
-    if (op->npts && t % op->decim == 0) return true;
+    if (dft_samples_at(*op, t)) return true;
   return false;
 }
 

@@ -541,6 +541,7 @@ int mnl_fields_set_time(mnl_fields *F, long long t) {
   F->t = t;
   if (F->twin) F->twin->t = t;
   probe_restart(F);
+  ldos_restart(F);
   return 0;
 }
 
@@ -1014,6 +1015,53 @@ int mnl_fields_remove_probes(mnl_fields *F) {
   if (!F) return fail("null fields");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   return probe_remove_all(F);
+}
+
+int mnl_fields_add_ldos(mnl_fields *F, const double *freqs, int nfreq, int *handle) {
+  if (!F || !freqs || !handle) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  if (refuse_complex(F, "add_ldos")) return -1;
+  const int h = ldos_add(F, freqs, nfreq);
+  if (h < 0) return -1;
+  *handle = h;
+  return 0;
+}
+
+int mnl_fields_ldos_update(mnl_fields *F, int h) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return ldos_update(F, h);
+}
+
+int mnl_fields_ldos_record(mnl_fields *F, int h, int on) {
+  if (!F) return fail("null fields");
+  return ldos_record(F, h, on);
+}
+
+int mnl_fields_ldos_data(mnl_fields *F, int h, double *ldos, double *Fdft, double *Jdft,
+                         double *overall_scale) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return ldos_data(F, h, ldos, Fdft, Jdft, overall_scale);
+}
+
+int mnl_fields_ldos_points(mnl_fields *F, int h, long long cap, long long *n, int *comp, int *ijk,
+                           double *amp) {
+  if (!F || !n) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return ldos_points(F, h, cap, n, comp, ijk, amp);
+}
+
+int mnl_fields_remove_ldos(mnl_fields *F, int h) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return ldos_remove(F, h);
+}
+
+int mnl_fields_remove_ldoses(mnl_fields *F) {
+  if (!F) return fail("null fields");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return ldos_remove_all(F);
 }
 
 int mnl_fields_dft_norm(mnl_fields *F, double *norm) {

@@ -125,6 +125,7 @@ struct SrcGroup {  // src_vol (src/meep_internals.hpp:49-82) over the whole cell
   int comp;        // E or H component
   int st;
   std::vector<long long> gidx;  // global canonical index of comp
+  std::vector<int> chunk;       // the reference chunk that holds the point (its src_vol's chunk)
   std::vector<int> jglob;       // 3 global indices per point
   std::vector<cplx> amp;
 };
@@ -211,8 +212,34 @@ struct DftChunkH {
   int shifti[3] = {0, 0, 0};  // periodic image chunk: the lattice shift from a loop point to
                               // the point of the region it stands for (dft_chunk::shift)
 };
-enum { DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4, DFT_PROBE = 5 };
+enum {
+  DFT_FLUX = 0, DFT_FIELDS = 1, DFT_N2F = 2, DFT_ENERGY = 3, DFT_FORCE = 4, DFT_PROBE = 5,
+  DFT_LDOS = 6
+};
 constexpr int DFT_MAXLISTS = 4;
+// dft_ldos (src/dft_ldos.cpp): what an object of kind DFT_LDOS has beside
+// the sampler's arrays.  The global point list (E list, then H list) follows the sources; slot =
+// list index, padded to an even count.
+struct LdosH {
+  std::vector<double> freq;
+  std::vector<cplx> Jdft;            // host data (the same on every rank)
+  double jsum_lists = 0.0;           // (sum |A| over both lists) * sqrt(dV) of the current lists
+  double jsum = 1.0;                 // Jsum of the last update (1.0 before the first)
+  bool rec = false;                  // record(on): every step appends an update
+  size_t nE = 0, nH = 0;             // points of the two lists
+  std::vector<int> comp, ijk;        // per list point: the component sampled, 3 global indices
+  std::vector<cplx> amp;             // ... and the source amplitude A
+  double *d_amp = nullptr;           // A per slot (re, im)
+  double *d_part = nullptr;          // [workgroup][update][4]
+  double *d_ej = nullptr;            // [update][4]: EJ, HJ of the buffered updates
+  double *d_F = nullptr;             // Fdft of this rank's points, [nfreq] complex
+  int nwg = 0;                       // the fixed split of the pairs of slots into workgroups
+  long long wg_pairs = 0;
+  ~LdosH() {
+    for (void *p : {(void *)d_amp, (void *)d_part, (void *)d_ej, (void *)d_F})
+      if (p) (void)hipFree(p);
+  }
+};
 struct DftFluxH {
   std::vector<double> omega;
   int nfreq = 0, decim = 1;
@@ -299,6 +326,10 @@ struct DftFluxH {
   int *d_pslot = nullptr;             // the points' slots in list order (-1: another rank's)
   int series_cap = 0;
   long long series_n = 0, series_t = 0;
+  // LDOS (kind DFT_LDOS): two lists, no DFT array; the object owns its device arrays as a probe
+  // does.  d_ph / ph_host hold one row per update: Ephase[nfreq], Hphase[nfreq] complex, then
+  // the first source's current and whether there was a source at all
+  std::unique_ptr<LdosH> ld;
   DftFluxH() = default;
   DftFluxH(const DftFluxH &) = delete;
   ~DftFluxH() {
@@ -309,7 +340,7 @@ struct DftFluxH {
                     (void *)d_ssel, (void *)d_spal, d_su, (void *)d_bad, (void *)d_cmp,
                     (void *)d_sci, (void *)d_norm_part, (void *)d_series, (void *)d_pslot})
       if (p) (void)hipFree(p);
-    if (kind == DFT_PROBE)
+    if (kind == DFT_PROBE || kind == DFT_LDOS)
       for (void *p : {(void *)d_pj, (void *)d_pch, (void *)d_pw, (void *)d_ch, (void *)d_fr})
         if (p) (void)hipFree(p);
   }
@@ -506,6 +537,8 @@ struct mnl_fields {
   std::vector<uint8_t> h_hsep_zone;  // host copy of DevFields::hsep_zone (27 zone boxes)
   // sources
   std::vector<SrcTime> srcs;
+  long long src0_born = 0;  // step count at which the first src_time was created: its cached
+                            // current is 0 until a step has run calc_sources on it
   std::vector<SrcGroup> groups;
   bool src_dirty = true;
   std::vector<long long> srcB_idx, srcD_idx, isrc_idx;  // local linear indices
@@ -549,6 +582,9 @@ struct mnl_fields {
   // leaves an empty entry.  sampled: what every step samples -- the DFT objects, then the probes
   std::vector<std::unique_ptr<DftFluxH>> probes;
   std::vector<DftFluxH *> sampled;
+  // LDOS objects (mnl_ldos.cpp): their own list and handles, sampled after the probes while they
+  // record or take an explicit update; a removed one leaves an empty entry
+  std::vector<std::unique_ptr<DftFluxH>> ldoses;
   double *d_norm_out = nullptr;  // dft_norm's per-object sums
   size_t norm_out_cap = 0;
 
@@ -881,8 +917,14 @@ int dft_flush(mnl_fields *F, DftFluxH &o);
 long long dft_plan_key(const mnl_fields *F);
 // cstate >= 0: a pair's middle (0) or new (1) state, whose two-step points are also in the
 // monitors' compact boxes
-int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1);
+// only: sample this object alone, whether it records or not (an explicit LDOS update)
+int dft_update(mnl_fields *F, long long t, const DevFields *fields = nullptr, int cstate = -1,
+               DftFluxH *only = nullptr);
 bool dft_due(const mnl_fields *F, long long t);
+// sampled by the step that reaches step count t: an LDOS object only while it records
+inline bool dft_samples_at(const DftFluxH &o, long long t) {
+  return o.npts && t % o.decim == 0 && (o.kind != DFT_LDOS || o.ld->rec);
+}
 int dft_flux_values(mnl_fields *F, int h, double *out);
 int dft_add_energy(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,
                    int decimation);
@@ -912,6 +954,21 @@ int probe_remove_all(mnl_fields *F);
 int dft_norm(mnl_fields *F, double *out);
 double dft_maxfreq(const mnl_fields *F);
 int dft_max_decimation(const mnl_fields *F);
+// ---- mnl_ldos.cpp: LDOS spectra (dft_ldos)
+constexpr int LDOS_BASE = 1 << 29;  // handles of LDOS objects: [LDOS_BASE, PROBE_BASE)
+int ldos_add(mnl_fields *F, const double *freqs, int nfreq);
+int ldos_update(mnl_fields *F, int h);
+int ldos_record(mnl_fields *F, int h, int on);
+int ldos_data(mnl_fields *F, int h, double *ldos, double *Fout, double *Jout, double *scale);
+int ldos_points(mnl_fields *F, int h, long long cap, long long *n, int *comp, int *ijk,
+                double *amp);
+int ldos_remove(mnl_fields *F, int h);
+int ldos_remove_all(mnl_fields *F);
+int ldos_flush(mnl_fields *F, DftFluxH &o);
+int ldos_prepare(mnl_fields *F, long long t0, int ns);  // phase rows of a chunk's updates
+void ldos_sampled(mnl_fields *F, DftFluxH &o);          // an update was taken
+int ldos_sources_rebuilt(mnl_fields *F);                // the source lists were rebuilt
+void ldos_restart(mnl_fields *F);
 int dft_save(mnl_fields *F, int h, const char *path);
 int dft_load_file(mnl_fields *F, int h, const char *path, int sign);
 int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const double *freqs, int nfreq,

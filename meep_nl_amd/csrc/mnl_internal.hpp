@@ -512,6 +512,14 @@ constexpr int NORM_WAVES = 4;          // waves per workgroup (a wave takes whol
 constexpr int NORM_MAX_WG = 1024;      // workgroups per object at most
 constexpr int NORM_WG_BLOCKS = 16;     // 64-slot blocks per workgroup at least
 
+// LDOS (dft_ldos): per buffered update the sums of f * conj(A) over the
+// electric and the magnetic source points.  A thread takes pairs of adjacent slots (one 16-byte
+// load per row), a workgroup a fixed range of pairs decided by the object's size alone.
+constexpr int LDOS_WAVES = 2;          // waves per workgroup
+constexpr int LDOS_UT = 8;             // updates per workgroup (grid y): A is read once per tile
+constexpr int LDOS_MAX_WG = 1024;      // slot ranges (workgroups along x) per object at most
+constexpr int LDOS_WG_PAIRS = 128;     // pairs of slots per slot range at least
+
 // =============================================================== launchers
 // Host-side launchers of the kernels, one heading per kernel file.  Each but k_cu_count
 // returns 0, or a non-zero code when an argument is bad or the launch failed.
@@ -622,6 +630,16 @@ int k_dft_norm(const double *dft, const int *pj, long long npts, int nfreq, long
 // points added in list order (pslot[i]: slot of list point i, -1 another rank's)
 int k_probe_append(const double *fr, long long npts, int n, const int *pslot, int nlist,
                    double *series, int cap, int start, void *stream);
+// LDOS: part[wg][u][4] = the workgroup's sums of fr[u][slot] * conj(amp[slot]) over its range of
+// this rank's slots (pj >= 0), (re, im) of the slots below nE and (re, im) of the others, for the
+// n buffered rows fr[u][npad] (npad even); k_n2f_reduce adds them in workgroup order
+int k_ldos_reduce(const double *fr, const double *amp, const int *pj, long long npad, long long nE,
+                  int n, long long wg_pairs, int nwg, double *part, void *stream);
+// LDOS: F[i] += Ephase[u][i] * EJ_u + Hphase[u][i] * HJ_u for u = 0..n-1 in update order, each
+// product as std::complex forms it; ej[u][4] = (EJ, HJ), row u of ph = Ephase[nfreq] then
+// Hphase[nfreq] complex, rstride doubles apart
+int k_ldos_accum(const double *ej, const double *ph, long long rstride, int n, int nfreq, double *F,
+                 void *stream);
 
 // ---- mnl_kernels_io.hip: what mnl_io.cpp and the ABI's getters launch
 int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,

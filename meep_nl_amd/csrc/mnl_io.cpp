@@ -161,6 +161,7 @@ int fields_load(mnl_fields *F, const char *path) {
   if (matched != nfield) return fail("fields file does not match these fields (allocated arrays differ)");
   F->t = h.t;
   probe_restart(F);  // probes are not part of a dump: empty at the loaded step
+  ldos_restart(F);   // nor are LDOS objects: their buffered rows are dropped
   // the loaded state comes from fields that were stepped: H and the W fields are
   // already separate (a dump taken before the first step holds zeros in them)
   F->e_first_done = F->h_first_done = true;

@@ -1,7 +1,7 @@
 // mnl_kernels_dft.hip -- gfx950 kernels of the DFT monitors (mnl_dft.cpp): the sampler, the
 // sampling plan, the accumulators, gather / scatter / scale of DFT data in list order, the
-// near-to-far-field transform and the pair sums of the energy and force monitors, with their
-// launchers.
+// near-to-far-field transform, the pair sums of the energy and force monitors and the LDOS
+// sums over the source points, with their launchers.
 #include "mnl_device.hpp"
 
 namespace mnl {
@@ -841,6 +841,119 @@ int k_probe_append(const double *fr, long long npts, int n, const int *pslot, in
     return 2;
   probe_append_kernel<<<(unsigned)((n + 63) / 64), 64, 0, (hipStream_t)stream>>>(
       fr, npts, n, pslot, nlist, series, cap, start);
+  return rc();
+}
+
+// ------------------------------------------------- LDOS
+// dft_ldos::update's sums over the source points (src/dft_ldos.cpp:107-149) for the buffered
+// updates: EJ_u = sum fr[u][s] * conj(A[s]) over the slots below nE, HJ_u over the others.  A
+// thread takes pairs of adjacent slots -- the rows are npad (even) doubles long, so a pair is one
+// aligned 16-byte load and a wave reads 1 KB in a row -- keeps the pair's amplitudes in registers
+// and walks a tile of UT updates (grid y), so that A is read once per tile, not once per update.
+// Four accumulators per update; one wave reduction in registers and one LDS pass over the waves
+// in wave order.  No atomics: part[wg][u][4] is added in workgroup order by n2f_reduce_kernel,
+// and a workgroup's range of pairs depends on the object alone, so the sums of one update are
+// the same bits wherever its row stands in the buffer and in every stepping mode.  A slot of
+// another rank or of the padded tail (pj < 0) is never added, not even as 0 * value.
+template <int UT>
+__global__ void __launch_bounds__(64 * LDOS_WAVES)
+    ldos_reduce_kernel(const double *__restrict__ fr, const double2 *__restrict__ amp,
+                       const int *__restrict__ pj, long long npad, long long nE, int n,
+                       long long wg_pairs, double *__restrict__ part) {
+  __shared__ double red[LDOS_WAVES][UT * 4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int u0 = blockIdx.y * UT;
+  const long long q0 = (long long)blockIdx.x * wg_pairs, q1 = min(q0 + wg_pairs, npad >> 1);
+  double acc[UT][4];
+#pragma unroll
+  for (int w = 0; w < UT; w++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[w][j] = 0.0;
+  for (long long q = q0 + threadIdx.x; q < q1; q += 64 * LDOS_WAVES) {
+    const long long s = 2 * q;
+    const bool l0 = pj[3 * s] >= 0, l1 = pj[3 * (s + 1)] >= 0;
+    if (!l0 && !l1) continue;
+    const double2 a0 = amp[s], a1 = amp[s + 1];
+    const bool h0 = s >= nE, h1 = s + 1 >= nE;
+    double2 f[UT];
+#pragma unroll
+    for (int w = 0; w < UT; w++)  // tail tiles repeat the last row (not written)
+      f[w] = *reinterpret_cast<const double2 *>(fr + (long long)min(u0 + w, n - 1) * npad + s);
+#pragma unroll
+    for (int w = 0; w < UT; w++) {
+      const double r0 = f[w].x * a0.x, i0 = f[w].x * -a0.y;  // double * conj(A)
+      const double r1 = f[w].y * a1.x, i1 = f[w].y * -a1.y;
+      // (selects, not products with 0: a slot that is not added contributes an exact + 0.0)
+      acc[w][0] += (l0 && !h0) ? r0 : 0.0;
+      acc[w][1] += (l0 && !h0) ? i0 : 0.0;
+      acc[w][2] += (l0 && h0) ? r0 : 0.0;
+      acc[w][3] += (l0 && h0) ? i0 : 0.0;
+      acc[w][0] += (l1 && !h1) ? r1 : 0.0;
+      acc[w][1] += (l1 && !h1) ? i1 : 0.0;
+      acc[w][2] += (l1 && h1) ? r1 : 0.0;
+      acc[w][3] += (l1 && h1) ? i1 : 0.0;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < UT; w++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const double v = n2f_wave_sum(acc[w][j]);
+      if (lane == 0) red[wave][w * 4 + j] = v;
+    }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < UT * 4 && u0 + t / 4 < n) {
+    double v = red[0][t];
+#pragma unroll
+    for (int k = 1; k < LDOS_WAVES; k++) v += red[k][t];
+    part[((long long)blockIdx.x * n + u0 + t / 4) * 4 + (t & 3)] = v;
+  }
+}
+
+// Fdft[i] += Ephase * EJ + Hphase * HJ (src/dft_ldos.cpp:150-153) for the buffered updates in
+// update order, one thread per frequency: each product as std::complex forms it (two products
+// and one sum or difference per part, no contraction), the two products added, then the sum
+// added to F -- the reference's operations in its order.  On the device so that a flush in the
+// middle of a batch needs no host round trip.
+__global__ void __launch_bounds__(64)
+    ldos_accum_kernel(const double *__restrict__ ej, const double *__restrict__ ph,
+                      long long rstride, int n, int nfreq, double2 *__restrict__ F) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nfreq) return;
+  double2 v = F[i];
+  for (int u = 0; u < n; u++) {
+    const double *__restrict__ r = ph + u * rstride;
+    const double ex = r[2 * i], ey = r[2 * i + 1];
+    const double hx = r[2 * (nfreq + i)], hy = r[2 * (nfreq + i) + 1];
+    const double ejx = ej[4 * u], ejy = ej[4 * u + 1], hjx = ej[4 * u + 2], hjy = ej[4 * u + 3];
+    const double er = ex * ejx - ey * ejy, ei = ex * ejy + ey * ejx;
+    const double hr = hx * hjx - hy * hjy, hi = hx * hjy + hy * hjx;
+    v.x = v.x + (er + hr);
+    v.y = v.y + (ei + hi);
+  }
+  F[i] = v;
+}
+
+int k_ldos_reduce(const double *fr, const double *amp, const int *pj, long long npad, long long nE,
+                  int n, long long wg_pairs, int nwg, double *part, void *stream) {
+  if (npad <= 0 || n <= 0) return 0;
+  if (!fr || !amp || !pj || !part || (npad & 1) || n > DFT_KB || nE < 0 || nE > npad ||
+      wg_pairs < 1 || nwg < 1 || nwg > LDOS_MAX_WG)
+    return 2;
+  if ((long long)nwg * wg_pairs < (npad >> 1)) return 2;  // every pair belongs to a workgroup
+  const dim3 grd((unsigned)nwg, (unsigned)((n + LDOS_UT - 1) / LDOS_UT));
+  ldos_reduce_kernel<LDOS_UT><<<grd, dim3(64 * LDOS_WAVES), 0, (hipStream_t)stream>>>(
+      fr, (const double2 *)amp, pj, npad, nE, n, wg_pairs, part);
+  return rc();
+}
+
+int k_ldos_accum(const double *ej, const double *ph, long long rstride, int n, int nfreq, double *F,
+                 void *stream) {
+  if (n <= 0) return 0;
+  if (!ej || !ph || !F || n > DFT_KB || nfreq < 1 || rstride < 4LL * nfreq) return 2;
+  ldos_accum_kernel<<<(unsigned)((nfreq + 63) / 64), 64, 0, (hipStream_t)stream>>>(
+      ej, ph, rstride, n, nfreq, (double2 *)F);
   return rc();
 }
 

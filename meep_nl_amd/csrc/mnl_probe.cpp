@@ -19,6 +19,8 @@ void dft_sampled_rebuild(mnl_fields *F) {
   for (auto &o : F->dfts) F->sampled.push_back(o.get());
   for (auto &o : F->probes)
     if (o) F->sampled.push_back(o.get());
+  for (auto &o : F->ldoses)
+    if (o) F->sampled.push_back(o.get());
   for (DftFluxH *o : F->sampled) o->cmp_on = false;
 }
 

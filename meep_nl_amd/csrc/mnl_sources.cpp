@@ -13,6 +13,7 @@ namespace mnlh {
 // of `where` it stands for.
 struct CLoop {
   int isc[3], iec[3], shifti[3];
+  int chunk = 0;  // index of the reference chunk
   cplx ph = 1.0;  // the lattice shift's Bloch phase (src/loop_in_chunks.cpp:409-416)
   double s0[3], s1[3], e0[3], e1[3];
   double W(int d, long i) const {  // IVEC_LOOP_WEIGHT1x (src/meep/vec.hpp:372-378)
@@ -42,8 +43,10 @@ static std::vector<CLoop> chunk_loops(const mnl_structure &S, const bool per[3],
   if (eikna)  // complex fields: ph *= pow(eikna[d], ishift[d]) over the directions
     for (int d = 0; d < 3; d++)
       if (S.has[d]) ph *= pow(eikna[d], ls.cur[d]);
+  int nchunk = 0;
   for (auto &ch : reference_chunks(S)) {
     CLoop L;
+    L.chunk = nchunk++;
     L.ph = ph;
     bool emp = false;
     for (int d = 0; d < 3; d++) {
@@ -172,6 +175,7 @@ static int add_volume_source(mnl_fields *F, int c, int st, const double wmin0[3]
           }
           grp.amp.push_back(wgt * (amp * std::conj(L.ph)) * A);  // src/sources.cpp:259
           grp.gidx.push_back(gi);
+          grp.chunk.push_back(L.chunk);
           for (int d = 0; d < 3; d++) grp.jglob.push_back(jg[d]);
         }
   }
@@ -366,7 +370,8 @@ int build_source_lists(mnl_fields *F) {
   }
   HIPCHK(hipStreamSynchronize(F->stream));
   F->src_dirty = false;
-  return 0;
+  // LDOS objects follow the sources: buffered rows flushed with the old lists, then new lists
+  return F->ldoses.empty() ? 0 : ldos_sources_rebuilt(F);
 }
 
 // SrcDev of field type t (0 = B, 1 = D) reading the group currents at J
@@ -555,6 +560,7 @@ int add_source_any(mnl_fields *F, int comp, int kind, const double *p, int np, m
   for (size_t i = 0; i < F->srcs.size(); i++)
     if (F->srcs[i].same(st)) idx = (int)i;
   if (idx < 0) {
+    if (F->srcs.empty()) F->src0_born = F->t;
     F->srcs.push_back(st);
     idx = (int)F->srcs.size() - 1;
   }

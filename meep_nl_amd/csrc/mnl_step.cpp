@@ -907,6 +907,7 @@ static int step_batch(mnl_fields *F, int nsteps) {
   for (int s0 = 0; s0 < nsteps; s0 += NAN_CH) {  // a chunk: one source table, one NaN flag read
     const int ns = std::min(NAN_CH, nsteps - s0);
     if (!F->dfts.empty() && dft_prepare(F, F->t, ns)) return -1;
+    if (!F->ldoses.empty() && ldos_prepare(F, F->t, ns)) return -1;
     if (source_table(F, F->t, ns, row)) return -1;
     for (int s = 0; s < ns; s++) {
       F->f.nr_t = F->t + s;  // seeds of the NR random fallback (nr_voxel_seed)

@@ -100,6 +100,7 @@ static int tb_plan(mnl_fields *F) {
   std::vector<DftFluxH *> cmon;  // monitors whose box the two-step kernel stores compactly
   for (DftFluxH *op : F->sampled) {  // (built once per monitor: this runs every batch)
     if (op->bbox.hi[0] < 0) continue;
+    if (op->kind == DFT_LDOS && !op->ld->rec) continue;  // idle: no step samples it
     if (F->dft_cmp && op->cmp_cells && (int)cmon.size() < TB_MAXCMP)
       cmon.push_back(op);
     else

@@ -702,6 +702,105 @@ def _data_to_str(d):  # python/simulation.py:5492-5497
     return str(d)
 
 
+class Ldos:
+    """python/simulation.py:5942-5954 (meep.Ldos -> dft_ldos, src/dft_ldos.cpp):
+    Ldos(fcen, df, nfreq), Ldos(freq) or Ldos(freq=[...]).  The object attaches to the
+    simulation's fields at its first use (core.Fields.add_ldos), so it may be created before
+    init_sim; the sums over the source points and the accumulation run on the device
+    (DESIGN.md section 34)."""
+
+    def __init__(self, *args, freq=None):
+        if freq is not None:
+            args = (list(freq) if isinstance(freq, tuple) else freq,)
+        if not args:
+            raise TypeError("add_dft functions only accept fcen,df,nfreq (3 numbers) or freq "
+                            "(array/list)")
+        args = fix_dft_args(args, 0)
+        self.freq = np.array(args[0], dtype=np.float64).ravel()
+        self._fields = None
+        self._handle = None
+
+    def _attach(self, sim):
+        sim.init_sim()
+        if self._fields is not sim.fields:
+            self._fields = sim.fields
+            self._handle = sim.fields.add_ldos(self.freq)
+        return self._handle
+
+    def update(self, sim):
+        """dft_ldos::update(fields)."""
+        sim.fields.ldos_update(self._attach(sim))
+
+    def record(self, sim, on):
+        sim.fields.ldos_record(self._attach(sim), on)
+
+    def data(self, sim):
+        """(ldos, F, J, overall_scale)"""
+        return sim.fields.ldos_data(self._attach(sim))
+
+    def ldos(self, sim):
+        return self.data(sim)[0]
+
+    def F(self, sim):
+        return self.data(sim)[1]
+
+    def J(self, sim):
+        return self.data(sim)[2]
+
+    def overall_scale(self, sim):
+        return self.data(sim)[3]
+
+
+def get_ldos_freqs(l):
+    """python/simulation.py:6006-6011"""
+    return [float(f) for f in l.freq]
+
+
+class _DftLdosStep:
+    """The step function dft_ldos returns (python/simulation.py:5983-5994): an update per
+    'step', the results into the Simulation at 'finish'.  When every top-level step function of
+    a run is one of these, _run_until takes the updates on the device while it steps in batches
+    instead of calling this once per step."""
+
+    def __init__(self, ldos):
+        self.ldos = ldos
+
+    def __call__(self, sim, todo):
+        ldos = self.ldos
+        if todo == "step":
+            ldos.update(sim)
+        else:
+            data, F, J, scale = ldos.data(sim)
+            sim.ldos_data = list(data)
+            sim.ldos_Fdata = list(F)
+            sim.ldos_Jdata = list(J)
+            sim.ldos_scale = scale
+            if verbosity.meep > 0 and sim._is_master():
+                display_csv(sim, "ldos", zip(get_ldos_freqs(ldos), sim.ldos_data))
+
+
+def dft_ldos(*args, **kwargs):
+    """python/simulation.py:5957-5994: dft_ldos(fcen, df, nfreq), dft_ldos(freq=...) or
+    dft_ldos(ldos=my_Ldos): the power spectrum of the sources normalised to the LDOS.  After the
+    run sim.ldos_data, sim.ldos_Fdata, sim.ldos_Jdata and sim.ldos_scale hold the results, and
+    the spectrum is printed as "ldos:," lines."""
+    ldos = kwargs.get("ldos", None)
+    if ldos is None:
+        if "freq" in kwargs and not args:
+            args = (kwargs["freq"],)
+        msg = ("dft_ldos only accepts freq_min,freq_max,nfreq (3 numbers) or freq (array/list) "
+               "or ldos (keyword argument)")
+        if not args:
+            raise TypeError(msg)
+        args = fix_dft_args(args, 0)
+        freq = args[0]
+        if isinstance(freq, (np.ndarray, list)):
+            ldos = Ldos(freq)
+        else:
+            raise TypeError(msg)
+    return _DftLdosStep(ldos)
+
+
 def display_csv(sim, name, data):
     """python/simulation.py:5463-5506: one "name<run_index>:, a, b, ..." line per row."""
     for row in data:
@@ -712,6 +811,8 @@ def display_csv(sim, name, data):
 
 # ---------------------------------------------------------------- step functions
 def _num_args(func):
+    if isinstance(func, _DftLdosStep):
+        return 2
     code = getattr(func, "__code__", None)
     if code is None:
         return 1
@@ -1184,6 +1285,7 @@ class Simulation:
         # fused 512^3 step, profiles/README.md)
         self.time_phases = bool(time_phases)
         self.run_index = 0
+        self.batched_runs = 0  # runs that went through _run_until_batched
         self.fields = None
         self.structure = None
         self.dft_objects = []
@@ -1497,10 +1599,15 @@ class Simulation:
             self._run_finished()
             return
         # (complex fields have no probes yet: their conditions go through the one-step loop)
-        if not step_funcs and not (self.complex_fields and
-                                   any(isinstance(c, _Condition) for c in conds)) and all(
+        # Step functions that are all dft_ldos objects (each with its own Ldos) do not force the
+        # one-step loop: their updates are taken on the device during the batches
+        ldos_only = (all(isinstance(f, _DftLdosStep) for f in step_funcs) and
+                     len({id(f.ldos) for f in step_funcs}) == len(step_funcs) and
+                     not self.complex_fields)
+        if (not step_funcs or ldos_only) and not (
+                self.complex_fields and any(isinstance(c, _Condition) for c in conds)) and all(
                 isinstance(c, (numbers.Number, _Condition)) for c in conds):
-            self._run_until_batched(conds, t0)
+            self._run_until_batched(conds, t0, step_funcs)
             return
         for i, c in enumerate(conds):
             if isinstance(c, numbers.Number):
@@ -1518,20 +1625,29 @@ class Simulation:
             _eval_step_func(self, fn, "finish")
         self._run_finished()
 
-    def _run_until_batched(self, conds, t0):
+    def _run_until_batched(self, conds, t0, ldos_steps=()):
         """The loop of _run_until for conditions that are numbers or speak the batched protocol
-        (no step functions): the same states go through the same conditions in the same order,
-        but fields.step is called once per stretch in which every condition only watches the
-        clock, and what the conditions would have read meanwhile is replayed from what the
-        device recorded."""
+        (no step functions but dft_ldos objects): the same states go through the same conditions
+        in the same order, but fields.step is called once per stretch in which every condition
+        only watches the clock, and what the conditions would have read meanwhile is replayed
+        from what the device recorded.  The dft_ldos objects take the
+        updates of the one-step loop -- the state before every step and the last one -- as one
+        explicit update of the starting state and a recorded update after every step (DESIGN.md
+        section 34)."""
+        self.batched_runs = getattr(self, "batched_runs", 0) + 1
         shows = [_progress(t0, c, self.progress_interval) for c in conds
                  if isinstance(c, numbers.Number)]
         conds = [_AfterTime(t0 + c) if isinstance(c, numbers.Number) else c for c in conds]
         # the state the run starts from: evaluated as the one-step loop does
-        if not any(c(self) for c in conds):
+        held = any(c(self) for c in conds)
+        for f in ldos_steps:
+            f.ldos.update(self)
+        if not held:
             t, dt = self.fields.t, self.fields.dt
             begun = []
             try:
+                for f in ldos_steps:
+                    f.ldos.record(self, True)
                 for c in conds:
                     c.batch_begin(self)
                     begun.append(c)
@@ -1552,8 +1668,12 @@ class Simulation:
                     for show in shows:
                         show(self)
             finally:
+                for f in ldos_steps:
+                    f.ldos.record(self, False)
                 for c in begun:
                     c.batch_end(self)
+        for f in ldos_steps:
+            f(self, "finish")
         self._run_finished()
 
     def _is_master(self):
