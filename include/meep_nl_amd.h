@@ -604,6 +604,33 @@ int mnl_fields_ldos_points(mnl_fields *f, int handle, long long cap, long long *
  * dropped with it. */
 int mnl_fields_remove_ldos(mnl_fields *f, int handle);
 int mnl_fields_remove_ldoses(mnl_fields *f);
+/* Replaces fields::get_eigenmode_coefficients(flux, eig_vol, ..., dp) (src/mpb.cpp:925-1004) for
+ * DiffractedPlanewave modes (get_eigenmode with dp != NULL, src/mpb.cpp:342-347, 619-664: an
+ * analytic plane wave, no eigensolver).  handle: a flux object with one region.  Per mode m:
+ * g[3 m ..] the diffraction order, axis[3 m ..] (axis NULL or all 0: the first direction lying in
+ * the plane of the monitor), sp[4 m ..] = s (re, im), p (re, im).  eig_vol: (min[3], max[3]) of
+ * the eigenmode volume, NULL = the flux region; kpoint[3], NULL = 0.  Outputs per (mode,
+ * frequency): coeffs[nmodes][nfreq][2] complex (forward, backward), vgrp, kpoints[..][3], cscale
+ * (each may be NULL but coeffs), and overlaps[nmodes][nfreq][8] complex (may be NULL): the four
+ * mode-flux sums of fields::get_overlap (src/dft.cpp:1377-1427: ExHy, EyHx, HyEx, HxEy for a z
+ * normal) and the four mode-mode sums.  The sums are taken on the device from the DFT array
+ * (buffered updates are accumulated first) in a fixed order and summed over the ranks
+ * (collective).  Evanescent orders give 0 everywhere, as src/mpb.cpp:957-962. */
+int mnl_fields_mode_coefficients(mnl_fields *f, int handle, int nmodes, const int *g,
+                                 const double *axis, const double *sp, const double *eig_vol,
+                                 const double *kpoint, double *coeffs, double *vgrp,
+                                 double *kpoints, double *cscale, double *overlaps);
+/* Diagnostic: the host table the call above hands to the device (arguments as there).
+ * dims[4] = na, nb (entries of the two in-plane phase tables), the number of normal layers, and
+ * 4 * da + db (the in-plane directions; db = 3: none).  Every other output may be NULL:
+ * coords[na + nb + 2] the integer half-pixel coordinates of the table entries and of the two
+ * layers; k[nmodes][nfreq][3]; vgrp[nmodes][nfreq]; amp[nmodes][nfreq][6] complex (Ex .. Hz);
+ * pa[nmodes][na], pb[nmodes][nb], pl[nmodes][nfreq][2] complex: exp(2 pi i k_d (x_d - centre_d))
+ * along the two in-plane directions and the normal. */
+int mnl_fields_mode_table(mnl_fields *f, int handle, int nmodes, const int *g, const double *axis,
+                          const double *sp, const double *eig_vol, const double *kpoint,
+                          long long *dims, int *coords, double *k, double *vgrp, double *amp,
+                          double *pa, double *pb, double *pl);
 /* fields::dft_norm() (src/dft.cpp:312-361): the square root of the sum of |dft|^2 over every
  * frequency and point of every chunk list of every DFT object (flux, fields, near2far, energy,
  * force; not probes), reduced on the device in a fixed order and summed over the ranks

@@ -20,6 +20,7 @@ from .simulation import (ALL, AUTOMATIC, Block, ContinuousSource, CustomSource, 
                          get_magnetic_energy, get_total_energy, scale_energy_fields,
                          scale_force_fields,
                          Ldos, dft_ldos, get_ldos_freqs,
+                         DiffractedPlanewave,
                          stop_when_fields_decayed, stop_when_energy_decayed,
                          stop_when_dft_decayed, vacuum, when_false, when_true, verbosity,
                          quiet, wall_time)

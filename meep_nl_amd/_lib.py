@@ -137,6 +137,10 @@ _SIGS = {
     "mnl_fields_ldos_points": (c_int, [c_void, c_int, ctypes.c_longlong, llptr, iptr, iptr, dptr]),
     "mnl_fields_remove_ldos": (c_int, [c_void, c_int]),
     "mnl_fields_remove_ldoses": (c_int, [c_void]),
+    "mnl_fields_mode_coefficients": (c_int, [c_void, c_int, c_int, iptr, dptr, dptr, dptr, dptr,
+                                             dptr, dptr, dptr, dptr, dptr]),
+    "mnl_fields_mode_table": (c_int, [c_void, c_int, c_int, iptr, dptr, dptr, dptr, dptr, llptr,
+                                      iptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mnl_fields_dft_norm": (c_int, [c_void, dptr]),
     "mnl_fields_dft_maxfreq": (c_int, [c_void, dptr]),
     "mnl_fields_max_decimation": (c_int, [c_void, iptr]),

@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, dptr, lib, ptr
+from ._lib import check, dptr, iptr, llptr, lib, ptr
 
 Ex, Ey, Ez, Hx, Hy, Hz, Dx, Dy, Dz, Bx, By, Bz = range(12)
 Dielectric, Permeability = 12, 13  # derived slice components (src/meep/vec.hpp:52-53)
@@ -1001,6 +1001,71 @@ class Fields:
         e, m = ctypes.c_double(), ctypes.c_double()
         check(lib().mnl_fields_near2far_medium(self.h, h, ctypes.byref(e), ctypes.byref(m)))
         return e.value, m.value
+
+    # -- mode coefficients of diffraction orders (fields::get_eigenmode_coefficients with a
+    #    DiffractedPlanewave, src/mpb.cpp:925-1004)
+    @staticmethod
+    def _mode_args(modes, eig_vol, kpoint):
+        """modes: [(g, axis or None, s, p)] -> the arrays of the two mode calls."""
+        modes = list(modes)
+        g = np.ascontiguousarray([[int(x) for x in m[0]] for m in modes],
+                                 dtype=np.intc).reshape(-1, 3)
+        axis = np.ascontiguousarray([[0.0, 0.0, 0.0] if m[1] is None else [float(x) for x in m[1]]
+                                     for m in modes], dtype=np.float64).reshape(-1, 3)
+        sp = np.ascontiguousarray([[complex(m[2]).real, complex(m[2]).imag, complex(m[3]).real,
+                                    complex(m[3]).imag] for m in modes],
+                                  dtype=np.float64).reshape(-1, 4)
+        ev = None if eig_vol is None else np.ascontiguousarray(
+            list(eig_vol[0]) + list(eig_vol[1]), dtype=np.float64)
+        kp = None if kpoint is None else np.ascontiguousarray(kpoint, dtype=np.float64)
+        return len(modes), g, axis, sp, ev, kp
+
+    def mode_coefficients(self, h, modes, eig_vol=None, kpoint=None):
+        """Coefficients of the flux object h in the plane waves modes = [(g, axis or None, s,
+        p)] (one launch for all of them), eig_vol = (min xyz, max xyz) or None for the flux
+        region, kpoint or None for 0.  Returns a dict: alpha complex (nmodes, nfreq, 2), vgrp
+        and cscale (nmodes, nfreq), kpoints (nmodes, nfreq, 3), overlaps complex (nmodes,
+        nfreq, 8): the four mode-flux and the four mode-mode sums of fields::get_overlap.
+        The sums are taken on the GPU and summed over ranks (collective)."""
+        nm, g, axis, sp, ev, kp = self._mode_args(modes, eig_vol, kpoint)
+        nf = getattr(self, "_dft_nf", {}).get(h, 1)
+        alpha = np.zeros((max(nm, 1), nf, 2), dtype=np.complex128)
+        vgrp = np.zeros((max(nm, 1), nf))
+        cscale = np.zeros((max(nm, 1), nf))
+        kpts = np.zeros((max(nm, 1), nf, 3))
+        ov = np.zeros((max(nm, 1), nf, 8), dtype=np.complex128)
+        check(lib().mnl_fields_mode_coefficients(
+            self.h, int(h), nm, g.ctypes.data_as(iptr), ptr(axis), ptr(sp), ptr(ev), ptr(kp),
+            ptr(alpha.view(np.float64)), ptr(vgrp), ptr(kpts), ptr(cscale),
+            ptr(ov.view(np.float64))))
+        return {"alpha": alpha, "vgrp": vgrp, "kpoints": kpts, "cscale": cscale, "overlaps": ov}
+
+    def mode_table(self, h, modes, eig_vol=None, kpoint=None):
+        """The host table mode_coefficients hands to the GPU (diagnostic).  Returns a dict:
+        dirs (da, db; db None when the plane is a line), coords_a, coords_b, layers (integer
+        half-pixel coordinates; a position is coordinate * 0.5 / a), k (nmodes, nfreq, 3), vgrp,
+        amp complex (nmodes, nfreq, 6), pa (nmodes, na), pb (nmodes, nb), pl (nmodes, nfreq, 2)."""
+        nm, g, axis, sp, ev, kp = self._mode_args(modes, eig_vol, kpoint)
+        nf = getattr(self, "_dft_nf", {}).get(h, 1)
+        dims = np.zeros(4, dtype=np.int64)
+        args = (self.h, int(h), nm, g.ctypes.data_as(iptr), ptr(axis), ptr(sp), ptr(ev), ptr(kp),
+                dims.ctypes.data_as(llptr))
+        check(lib().mnl_fields_mode_table(*args, None, None, None, None, None, None, None))
+        na, nb, nl = int(dims[0]), int(dims[1]), int(dims[2])
+        coords = np.zeros(na + nb + 2, dtype=np.intc)
+        k = np.zeros((nm, nf, 3))
+        vgrp = np.zeros((nm, nf))
+        amp = np.zeros((nm, nf, 6), dtype=np.complex128)
+        pa = np.zeros((nm, na), dtype=np.complex128)
+        pb = np.zeros((nm, nb), dtype=np.complex128)
+        pl = np.zeros((nm, nf, 2), dtype=np.complex128)
+        check(lib().mnl_fields_mode_table(
+            *args, coords.ctypes.data_as(iptr), ptr(k), ptr(vgrp), ptr(amp.view(np.float64)),
+            ptr(pa.view(np.float64)), ptr(pb.view(np.float64)), ptr(pl.view(np.float64))))
+        da, db = int(dims[3]) // 4, int(dims[3]) % 4
+        return {"dirs": (da, None if db == 3 else db), "coords_a": coords[:na].copy(),
+                "coords_b": coords[na:na + nb].copy(), "layers": coords[na + nb:na + nb + nl].copy(),
+                "k": k, "vgrp": vgrp, "amp": amp, "pa": pa, "pb": pb, "pl": pl}
 
 
 class LocalHub:

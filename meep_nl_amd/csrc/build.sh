@@ -5,7 +5,7 @@
 # (grid, PML, materials, quadrature), mnl_sources.cpp (sources, get_field), mnl_fused.cpp
 # (fused-tile planning), mnl_tb.cpp (pairs of steps), mnl_step.cpp (the step loop, NaN guard),
 # mnl_tune.cpp (the tuner), mnl_dft.cpp (DFT monitors), mnl_probe.cpp (field probes, dft_norm),
-# mnl_ldos.cpp (LDOS spectra), mnl_io.cpp (checkpoints, slices, energy),
+# mnl_ldos.cpp (LDOS spectra), mnl_modes.cpp (mode coefficients), mnl_io.cpp (checkpoints, slices, energy),
 # mnl_stats.cpp (kernel statistics, the byte model), mnl_comm.cpp (RCCL / IPC).
 # All compiles run at once (at most MNL_JOBS, default 16), then one link.
 set -e
@@ -18,7 +18,7 @@ ARCH=${MNL_ARCH:-gfx950}
 JOBS=${MNL_JOBS:-16}
 CXXF="$MNL_KFLAGS -O2 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I$ROCM/include"
 KERNEL_SRCS="mnl_kernels mnl_kernels_setup mnl_kernels_dft mnl_kernels_io"
-HOST_SRCS="mnl_host mnl_setup mnl_sources mnl_fused mnl_tb mnl_step mnl_tune mnl_dft mnl_probe mnl_ldos mnl_io mnl_stats mnl_comm"
+HOST_SRCS="mnl_host mnl_setup mnl_sources mnl_fused mnl_tb mnl_step mnl_tune mnl_dft mnl_probe mnl_ldos mnl_modes mnl_io mnl_stats mnl_comm"
 OBJS=""
 PIDS=""
 # set -e does not see a background job fail: every job's status is taken from wait on its pid

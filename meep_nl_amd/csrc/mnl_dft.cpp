@@ -368,6 +368,7 @@ int dft_add_flux(mnl_fields *F, int nreg, const double *regions, const double *f
   o->decim = dft_decimation(F, freqs, nfreq, decimation);
   for (int d = 0; d < 3; d++) o->wmin[d] = regions[d], o->wmax[d] = regions[3 + d];
   o->kb = dft_block();
+  o->nreg = nreg, o->normal = int(regions[6]);
   const double dt_factor = F->dt / sqrt(2.0 * pi) * o->decim;
   std::vector<double> pwE, pwH;
   DftFluxH ho;  // H points collected separately, appended after the E points
@@ -640,7 +641,7 @@ int dft_points(mnl_fields *F, int h, int which, double *out, long long npoints) 
 // ------------------------------------------------------------------ near2far
 // fields::get_eps / get_mu (src/monitor.cpp:202-224): the number of components over the
 // trace of the interpolated diagonal chi1inv at pos
-static double n2f_medium_at(const mnl_structure &S, int t, const double pos[3]) {
+double n2f_medium_at(const mnl_structure &S, int t, const double pos[3]) {
   double tr = 0;
   int nc = 0;
   for (int k = 0; k < 3; k++) {

@@ -793,6 +793,7 @@ int mnl_fields_use_bloch(mnl_fields *F, int dir, double k_re, double k_im) {
   if (mnl_fields *T = F->twin.get()) {
     if (T->fused && set_fused(T, false)) return -1;
     F->eikna[dir] = bloch_eikna(cplx(k_re, k_im), F->S.n[dir], F->S.a);
+    F->bloch_k[dir] = cplx(k_re, k_im);
     if (F->periodic[dir]) return 0;  // k set again
     if (set_periodic(T, dir)) return -1;
   }
@@ -1056,6 +1057,26 @@ int mnl_fields_remove_ldos(mnl_fields *F, int h) {
   if (!F) return fail("null fields");
   if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
   return ldos_remove(F, h);
+}
+
+int mnl_fields_mode_coefficients(mnl_fields *F, int h, int nmodes, const int *g, const double *axis,
+                                 const double *sp, const double *eig_vol, const double *kpoint,
+                                 double *coeffs, double *vgrp, double *kpoints, double *cscale,
+                                 double *overlaps) {
+  if (!F || !coeffs || (nmodes >= 1 && (!g || !sp))) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return mode_coefficients(F, ModeCall{h, nmodes, g, axis, sp, eig_vol, kpoint}, coeffs, vgrp,
+                           kpoints, cscale, overlaps);
+}
+
+int mnl_fields_mode_table(mnl_fields *F, int h, int nmodes, const int *g, const double *axis,
+                          const double *sp, const double *eig_vol, const double *kpoint,
+                          long long *dims, int *coords, double *k, double *vgrp, double *amp,
+                          double *pa, double *pb, double *pl) {
+  if (!F || !dims || (nmodes >= 1 && (!g || !sp))) return fail("null argument");
+  if (hipSetDevice(F->device) != hipSuccess) return fail("hipSetDevice failed");
+  return mode_table(F, ModeCall{h, nmodes, g, axis, sp, eig_vol, kpoint}, dims, coords, k, vgrp,
+                    amp, pa, pb, pl);
 }
 
 int mnl_fields_remove_ldoses(mnl_fields *F) {

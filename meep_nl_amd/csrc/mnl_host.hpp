@@ -330,6 +330,24 @@ struct DftFluxH {
   // does.  d_ph / ph_host hold one row per update: Ephase[nfreq], Hphase[nfreq] complex, then
   // the first source's current and whether there was a source at all
   std::unique_ptr<LdosH> ld;
+  // flux objects: the regions given and the first one's normal (dft_flux::normal_direction)
+  int nreg = 0, normal = -1;
+  // mode coefficients (mnl_modes.cpp): the per-slot index arrays, the slot
+  // ranges of the workgroups and the distinct coordinates the phase tables are built over;
+  // built at the first call (a flux object's slot arrays are never rebuilt), with the per-call
+  // tables, partial sums and results in buffers that grow
+  struct ModeIdx {
+    bool built = false;
+    int da = 0, db = -1, nlayer = 1, layer[2] = {0, 0};
+    std::vector<int> ca, cb;
+    int nwg = 0, wg0[5] = {0, 0, 0, 0, 0};  // workgroups wg0[j] .. wg0[j+1]-1 add to sum j
+    long long nslots = 0;
+    ModeSlot *d_slot = nullptr;
+    double *d_wv = nullptr;
+    ModeRange *d_rng = nullptr;
+    double *d_tab = nullptr, *d_part = nullptr, *d_out = nullptr;
+    size_t tab_cap = 0, part_cap = 0, out_cap = 0;
+  } mo;
   DftFluxH() = default;
   DftFluxH(const DftFluxH &) = delete;
   ~DftFluxH() {
@@ -338,7 +356,9 @@ struct DftFluxH {
                     (void *)d_ps_out, (void *)d_list, (void *)d_n2f_part,
                     (void *)d_n2f_xyz, (void *)d_n2f_out, (void *)d_ph, (void *)d_sidx,
                     (void *)d_ssel, (void *)d_spal, d_su, (void *)d_bad, (void *)d_cmp,
-                    (void *)d_sci, (void *)d_norm_part, (void *)d_series, (void *)d_pslot})
+                    (void *)d_sci, (void *)d_norm_part, (void *)d_series, (void *)d_pslot,
+                    (void *)mo.d_slot, (void *)mo.d_wv, (void *)mo.d_rng, (void *)mo.d_tab,
+                    (void *)mo.d_part, (void *)mo.d_out})
       if (p) (void)hipFree(p);
     if (kind == DFT_PROBE || kind == DFT_LDOS)
       for (void *p : {(void *)d_pj, (void *)d_pch, (void *)d_pw, (void *)d_ch, (void *)d_fr})
@@ -367,6 +387,7 @@ struct mnl_fields {
   std::unique_ptr<mnl_fields> twin;
   mnl_fields *part0 = nullptr;
   cplx eikna[3] = {1.0, 1.0, 1.0};
+  cplx bloch_k[3] = {0.0, 0.0, 0.0};  // fields::k of the periodic directions (part 0 holds it)
   DevGrid g;
   DevFields f;
   size_t nlocal = 0;  // doubles per local array
@@ -975,6 +996,18 @@ int dft_add_near2far(mnl_fields *F, int nreg, const double *regions, const doubl
                      int decimation, int nperiods);
 int n2f_farfields(mnl_fields *F, int h, long long npts, const double *xyz, double *out);
 int n2f_points(mnl_fields *F, int h, double *out, long long npoints);
+double n2f_medium_at(const mnl_structure &S, int t, const double pos[3]);  // get_eps / get_mu
+// ---- mnl_modes.cpp: mode coefficients of diffraction orders (get_eigenmode_coefficients with a
+// DiffractedPlanewave)
+struct ModeCall {  // the arguments of both entry points
+  int h, nmodes;
+  const int *g;
+  const double *axis, *sp, *eig_vol, *kpoint;
+};
+int mode_coefficients(mnl_fields *F, const ModeCall &c, double *coeffs, double *vgrp,
+                      double *kpoints, double *cscale, double *overlaps);
+int mode_table(mnl_fields *F, const ModeCall &c, long long dims[4], int *coords, double *k,
+               double *vgrp, double *amp, double *pa, double *pb, double *pl);
 
 // ---- mnl_io.cpp: checkpoints, array slices, field energy
 struct CkEntry {

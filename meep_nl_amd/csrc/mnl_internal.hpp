@@ -520,6 +520,36 @@ constexpr int LDOS_UT = 8;             // updates per workgroup (grid y): A is r
 constexpr int LDOS_MAX_WG = 1024;      // slot ranges (workgroups along x) per object at most
 constexpr int LDOS_WG_PAIRS = 128;     // pairs of slots per slot range at least
 
+// Mode coefficients (get_eigenmode_coefficients with a DiffractedPlanewave, DESIGN.md section
+// 35): per (mode, frequency) the four mode-flux and the four mode-mode overlap sums of
+// fields::get_overlap over a flux object's slots.  A workgroup takes one range of this rank's
+// slots of one of the four sums; the ranges depend on the object alone.
+constexpr int MO_WAVES = 2;            // waves per workgroup
+constexpr int MO_MT = 2;               // modes per workgroup (grid z)
+constexpr int MO_FT = 4;               // frequencies per workgroup (grid y)
+constexpr int MO_MAX_WG = 1024;        // slot ranges per sum at most
+constexpr int MO_WG_SLOTS = 512;       // slots per range at least (a multiple of 64)
+struct ModeSlot {    // per slot
+  int ia, ib;        // index into the two in-plane phase tables
+  int layer;         // bit 0: the normal layer; bit 1: the chunk stored the loop weight
+  int pad;
+};
+struct ModeRange {   // per workgroup: slots [s0, s1) add to sum j (0..3)
+  int s0, s1, j, pad;
+};
+struct ModeArgs {
+  const double *dft;        // [slot/64][freq][slot%64] complex
+  const ModeSlot *slot;
+  const double *wv;         // per slot: the loop weight w, the stored weight
+  const ModeRange *rng;
+  const double *pa, *pb;    // [mode][na], [mode][nb] complex
+  const double *pl;         // [mode][freq][2] complex
+  const double *ac, *as;    // [mode][freq][4] complex: the amplitude of the conjugated
+                            // component of sum j, and of the sum's own component
+  int nmodes, nfreq, na, nb;
+  double *part;             // [workgroup][mode][freq][4]: mode-flux (re, im), mode-mode (re, im)
+};
+
 // =============================================================== launchers
 // Host-side launchers of the kernels, one heading per kernel file.  Each but k_cu_count
 // returns 0, or a non-zero code when an argument is bad or the launch failed.
@@ -640,6 +670,10 @@ int k_ldos_reduce(const double *fr, const double *amp, const int *pj, long long 
 // Hphase[nfreq] complex, rstride doubles apart
 int k_ldos_accum(const double *ej, const double *ph, long long rstride, int n, int nfreq, double *F,
                  void *stream);
+// mode coefficients: part[wg][mode][freq][4] = the workgroup's sums of w conj(mode) dft_val and
+// of w conj(mode) mode over its slot range (nslots: the size of the per-slot arrays);
+// k_n2f_reduce adds the workgroups of one sum in order
+int k_mode_overlap(const ModeArgs &a, int nwg, long long nslots, void *stream);
 
 // ---- mnl_kernels_io.hip: what mnl_io.cpp and the ABI's getters launch
 int k_energy(const double *A, const double *Asep, const double *Bv, const DevGrid &g,

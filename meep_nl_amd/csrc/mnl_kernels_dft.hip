@@ -957,6 +957,111 @@ int k_ldos_accum(const double *ej, const double *ph, long long rstride, int n, i
   return rc();
 }
 
+// ------------------------------------------------- mode coefficients
+// fields::get_overlap (src/dft.cpp:1377-1427) for a tile of MT modes x FT frequencies over one
+// workgroup's slot range: the terms of dft_chunk::process_dft_component (src/dft.cpp:977-1027),
+// w * conj(mode[c_conjugate](x)) * dft_val and w * conj(mode[c_conjugate](x)) * mode[c](x), of
+// the one sum the range's component adds to.  The mode is an analytic plane wave, so its value
+// is amplitude * phase with the phase the product of three table entries (mnl_modes.hpp): the
+// device only multiplies and adds.  Lanes are consecutive slots (a frequency is a contiguous
+// span of 16-byte values); each lane keeps its 4 doubles per (mode, frequency) in registers over
+// the range, then one wave reduction and one LDS pass in wave order.  No atomics: the ranges
+// hold this rank's slots only (other ranks' slots and the padded tail belong to no range) and
+// depend on the object alone, so a sum is the same bits in every call and every stepping mode.
+// Complex products as std::complex forms them (the file is built without contraction).
+__device__ __forceinline__ double2 mo_cmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+template <int MT, int FT>
+__global__ void __launch_bounds__(64 * MO_WAVES) mode_overlap_kernel(ModeArgs a) {
+  __shared__ double red[MO_WAVES][MT * FT * 4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int f0 = blockIdx.y * FT, m0 = blockIdx.z * MT;
+  const ModeRange r = a.rng[blockIdx.x];
+  const double2 *__restrict__ dft = (const double2 *)a.dft;
+  const double2 *__restrict__ wv = (const double2 *)a.wv;
+  const double2 *__restrict__ pa = (const double2 *)a.pa;
+  const double2 *__restrict__ pb = (const double2 *)a.pb;
+  const double2 *__restrict__ pl = (const double2 *)a.pl;
+  const double2 *__restrict__ ac = (const double2 *)a.ac;
+  const double2 *__restrict__ as = (const double2 *)a.as;
+  double acc[MT][FT][4];
+#pragma unroll
+  for (int q = 0; q < MT; q++)
+#pragma unroll
+    for (int w = 0; w < FT; w++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) acc[q][w][e] = 0.0;
+  for (int s = r.s0 + (int)threadIdx.x; s < r.s1; s += 64 * MO_WAVES) {
+    const ModeSlot ms = a.slot[s];
+    const double2 ww = wv[s];  // (w, stored weight)
+    const bool stored_w = (ms.layer & 2) != 0;
+    const int layer = ms.layer & 1;
+    const double2 *__restrict__ dp = dft + (long long)(s >> 6) * a.nfreq * 64 + (s & 63);
+    double2 d[FT];
+#pragma unroll
+    for (int w = 0; w < FT; w++) {  // tail tiles repeat the last frequency (not written)
+      double2 v = dp[(long long)min(f0 + w, a.nfreq - 1) * 64];
+      v.x = v.x / ww.y, v.y = v.y / ww.y;  // dft / stored_weight
+      if (stored_w && (v.x != 0.0 || v.y != 0.0)) v.x = v.x / ww.x, v.y = v.y / ww.x;
+      d[w] = v;
+    }
+#pragma unroll
+    for (int q = 0; q < MT; q++) {  // tail tiles repeat the last mode (not written)
+      const int m = min(m0 + q, a.nmodes - 1);
+      const double2 ab = mo_cmul(pa[(long long)m * a.na + ms.ia], pb[(long long)m * a.nb + ms.ib]);
+#pragma unroll
+      for (int w = 0; w < FT; w++) {
+        const long long mf = (long long)m * a.nfreq + min(f0 + w, a.nfreq - 1);
+        const double2 ph = mo_cmul(ab, pl[mf * 2 + layer]);
+        const double2 mc = mo_cmul(ac[mf * 4 + r.j], ph);  // mode[c_conjugate](x)
+        const double2 mo = mo_cmul(as[mf * 4 + r.j], ph);  // mode[c](x)
+        const double2 wc = make_double2(ww.x * mc.x, ww.x * -mc.y);  // w * conj(mode1val)
+        const double2 t = mo_cmul(wc, d[w]), u = mo_cmul(wc, mo);
+        acc[q][w][0] += t.x;
+        acc[q][w][1] += t.y;
+        acc[q][w][2] += u.x;
+        acc[q][w][3] += u.y;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < MT; q++)
+#pragma unroll
+    for (int w = 0; w < FT; w++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const double v = n2f_wave_sum(acc[q][w][e]);
+        if (lane == 0) red[wave][(q * FT + w) * 4 + e] = v;
+      }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < MT * FT * 4) {
+    const int q = t / (FT * 4), w = (t >> 2) % FT;
+    if (m0 + q < a.nmodes && f0 + w < a.nfreq) {
+      double v = red[0][t];
+#pragma unroll
+      for (int k = 1; k < MO_WAVES; k++) v += red[k][t];
+      a.part[(((long long)blockIdx.x * a.nmodes + m0 + q) * a.nfreq + f0 + w) * 4 + (t & 3)] = v;
+    }
+  }
+}
+
+int k_mode_overlap(const ModeArgs &a, int nwg, long long nslots, void *stream) {
+  if (nwg <= 0) return 0;
+  if (!a.dft || !a.slot || !a.wv || !a.rng || !a.pa || !a.pb || !a.pl || !a.ac || !a.as ||
+      !a.part || a.nmodes < 1 || a.nfreq < 1 || a.na < 1 || a.nb < 1 || nslots < 1 ||
+      nslots >= (1LL << 31))
+    return 2;
+  static_assert(MO_MT * MO_FT * 4 <= 64 * MO_WAVES, "one thread per partial sum");
+  const dim3 grd((unsigned)nwg, (unsigned)((a.nfreq + MO_FT - 1) / MO_FT),
+                 (unsigned)((a.nmodes + MO_MT - 1) / MO_MT));
+  if (grd.y > 65535 || grd.z > 65535) return 2;
+  mode_overlap_kernel<MO_MT, MO_FT><<<grd, dim3(64 * MO_WAVES), 0, (hipStream_t)stream>>>(a);
+  return rc();
+}
+
 int k_n2f_farfield(const N2FArgs &a, int nwg, void *stream) {
   if (a.npts <= 0 || nwg <= 0) return 0;
   if (a.nfreq < 1 || a.nruns < 1 || a.wg_blocks < 1) return 2;

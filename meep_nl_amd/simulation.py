@@ -331,6 +331,38 @@ AUTOMATIC = -1
 FluxData = namedtuple("FluxData", ["E", "H"])
 NearToFarData = namedtuple("NearToFarData", ["F"])
 ForceData = namedtuple("ForceData", ["offdiag1", "offdiag2", "diag"])
+# python/simulation.py:62: what get_eigenmode_coefficients returns
+EigCoeffsResult = namedtuple("EigCoeffsResult", ["alpha", "vgrp", "kpoints", "kdom", "cscale"])
+NO_PARITY = 0
+
+
+class DiffractedPlanewave:
+    """python/simulation.py:163-205: a diffracted planewave in a homogeneous medium, the `bands`
+    argument of get_eigenmode_coefficients.  g: the diffraction order (three integers); axis:
+    with the wavevector it spans the plane of incidence (None: the first direction lying in
+    the plane of the monitor); s, p: the complex amplitudes of the two polarisations."""
+
+    def __init__(self, g=None, axis=None, s=None, p=None):
+        self._g = g
+        self._axis = axis
+        self._s = complex(s)
+        self._p = complex(p)
+
+    @property
+    def g(self):
+        return self._g
+
+    @property
+    def axis(self):
+        return self._axis
+
+    @property
+    def s(self):
+        return self._s
+
+    @property
+    def p(self):
+        return self._p
 
 
 class _DftData:
@@ -1772,6 +1804,87 @@ class Simulation:
         flux._create()
         self.dft_objects.append(flux)
         return flux
+
+    # -- mode decomposition into diffraction orders (python/simulation.py:3507-3545, 4135-4229)
+    def add_mode_monitor(self, *args, **kwargs):
+        """add_mode_monitor(fcen, df, nfreq, *ModeRegions) or add_mode_monitor(freq,
+        *ModeRegions): the arguments of add_flux, and here the same object (the reference's
+        differs only in not using symmetries, which this build does not have)."""
+        return self.add_flux(*args, **kwargs)
+
+    def get_eigenmode_coefficients(self, flux, bands, eig_parity=NO_PARITY, eig_vol=None,
+                                   eig_resolution=0, eig_tolerance=1e-12, kpoint_func=None,
+                                   direction=AUTOMATIC):
+        """The coefficients of the fields of flux in diffracted planewaves.  bands is one
+        DiffractedPlanewave, as in Meep, or a list of them (an extension: every order is
+        projected in one GPU launch).  Returns alpha[len(bands), nfreq, 2] (forward, backward),
+        vgrp, kpoints, kdom and cscale, shaped as Meep's.  Integer band numbers need a mode
+        solver (MPB) and raise NotImplementedError.  eig_parity, eig_resolution and
+        eig_tolerance are accepted and ignored: a planewave is not solved for.
+        kpoint_func(freq, band_number) is evaluated per (band, frequency) on the host, with
+        band number 1 for every entry (what the reference passes for a DiffractedPlanewave);
+        the GPU is called once per distinct kpoint it returns, each call over all frequencies,
+        so a kpoint that depends on the frequency costs nfreq calls."""
+        if self.fields is None:
+            raise ValueError("Fields must be initialized before calling "
+                             "get_eigenmode_coefficients")
+        if isinstance(bands, DiffractedPlanewave):
+            dps = [bands]
+        elif isinstance(bands, (list, tuple, range)):
+            dps = list(bands)
+            if not dps or not all(isinstance(b, DiffractedPlanewave) for b in dps):
+                if dps and all(isinstance(b, numbers.Integral) for b in dps):
+                    raise NotImplementedError(
+                        "get_eigenmode_coefficients: integer band numbers need the MPB mode "
+                        "solver, which this build does not have; pass DiffractedPlanewave objects")
+                raise TypeError("get_eigenmode_coefficients: bands must be either a list or "
+                                "DiffractedPlanewave object")
+        elif isinstance(bands, numbers.Integral):
+            raise NotImplementedError(
+                "get_eigenmode_coefficients: integer band numbers need the MPB mode solver, "
+                "which this build does not have; pass DiffractedPlanewave objects")
+        else:
+            raise TypeError("get_eigenmode_coefficients: bands must be either a list or "
+                            "DiffractedPlanewave object")
+        if direction is not None and direction != AUTOMATIC:
+            r = flux.regions[0]
+            nd = _normal_direction(self.dimensions, r.size) if r.direction < 0 else r.direction
+            if direction != nd:
+                raise NotImplementedError("get_eigenmode_coefficients: a direction other than "
+                                          "the flux region's normal is not supported")
+        ev = None
+        if eig_vol is not None:
+            lo = [eig_vol.center[k] - 0.5 * eig_vol.size[k] for k in range(3)]
+            hi = [eig_vol.center[k] + 0.5 * eig_vol.size[k] for k in range(3)]
+            ev = (lo, hi)
+        modes = []
+        for b in dps:
+            if b.g is None or len(b.g) != 3:
+                raise ValueError("DiffractedPlanewave: g must be three integers")
+            modes.append((b.g, b.axis, b.s, b.p))
+        nb, nf = len(modes), len(flux.freq)
+        f = self.fields
+        if kpoint_func is None:
+            r = f.mode_coefficients(flux.handle, modes, ev, None)
+            alpha, vgrp, kpts, csc = r["alpha"], r["vgrp"], r["kpoints"], r["cscale"]
+        else:
+            # the kpoint of every (band, frequency); bands and frequencies that share one share a call
+            kps = {}
+            for ib in range(nb):
+                for i, fr in enumerate(flux.freq):
+                    kp = kpoint_func(fr, 1)
+                    kps.setdefault(tuple(float(x) for x in kp), []).append((ib, i))
+            alpha = np.zeros((nb, nf, 2), dtype=np.complex128)
+            vgrp, csc, kpts = np.zeros((nb, nf)), np.zeros((nb, nf)), np.zeros((nb, nf, 3))
+            for kp, where in kps.items():
+                ibs = sorted(set(ib for ib, _ in where))
+                r = f.mode_coefficients(flux.handle, [modes[ib] for ib in ibs], ev, kp)
+                for ib, i in where:
+                    j = ibs.index(ib)
+                    alpha[ib, i], vgrp[ib, i] = r["alpha"][j, i], r["vgrp"][j, i]
+                    csc[ib, i], kpts[ib, i] = r["cscale"][j, i], r["kpoints"][j, i]
+        kl = [Vector3(*k) for k in kpts.reshape(-1, 3)]
+        return EigCoeffsResult(alpha, vgrp.reshape(-1), kl, list(kl), csc.reshape(-1))
 
     # -- the DFT data of a flux object (python/simulation.py:3548-3635).  Files are flat binary
     # files (fields.dft_save), not HDF5; fname is used as given plus ".mnl".
